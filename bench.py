@@ -47,6 +47,14 @@ Fields of the full result:
                one kernel launch each.
 --only LEG runs one leg and nothing else (the rocprofv3 passes of
 profiles/profile_legs.sh); --legs chooses the legs of a full run.
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline needs:
+text, index, batch, W warm-up steps, K timed steps, the result line (metric, value, unit,
+steps, warmup, ms_per_step, dtype, config, the index's size).  Everything else above — the
+roofline (its accounting kernel and the PMC table), the legs, cpu_baseline, p50, the N > 1
+locate and the check of the gathered counts — runs under --full (--only and --legs imply it).
+--dump-outputs DIR writes what the last timed step returned to its caller as float64 .npy
+files (dump_outputs()); the inputs are seeded, so two builds can be compared array by array.
 """
 import argparse
 import json
@@ -300,6 +308,32 @@ def time_launches(launch, steps, warmup, stream):
     wall = (time.perf_counter() - t0) / steps
     ms = [a.elapsed_time(b) for a, b in evs]
     return wall, statistics.mean(ms) / 1e3, min(ms)
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_SAMPLE = 4_000_000  # counts kept of a batch too large to write whole (32 MB as float64)
+
+
+def dump_sample_index(n, k=None):
+    """The k (default DUMP_SAMPLE) positions of an n-element output that --dump-outputs keeps:
+    a fixed multiplicative hash of 0..k-1 (plain integer arithmetic, the same on every build)."""
+    k = DUMP_SAMPLE if k is None else k
+    return ((np.arange(k, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)) >> np.uint64(11)) % np.uint64(n)
+
+
+def dump_outputs(dirpath, counts):
+    """--dump-outputs: what the timed path's last step handed its caller — the batch's counts
+    (N > 1: rank 0's gathered counts of the global batch, in pattern order) — as float64 (exact
+    below 2^53).  counts.npy holds every count when they fit DUMP_MAX_BYTES, else the counts at
+    dump_sample_index(); counts_summary.npy = [patterns, sum of all counts, patterns found,
+    largest count] covers the whole output either way."""
+    os.makedirs(dirpath, exist_ok=True)
+    c = np.asarray(counts).astype(np.int64).ravel()
+    whole = c.size * 8 + 8192 <= DUMP_MAX_BYTES  # (8 KB: the two headers and the summary)
+    kept = c if whole else c[dump_sample_index(c.size).astype(np.int64)]
+    np.save(os.path.join(dirpath, "counts.npy"), kept.astype(np.float64))
+    np.save(os.path.join(dirpath, "counts_summary.npy"),
+            np.array([c.size, c.sum(), (c >= 1).sum(), c.max() if c.size else 0], np.float64))
 
 
 class Workload:
@@ -895,7 +929,13 @@ def main():
                     help="prefix-table depth override (0 = off; default automatic)")
     ap.add_argument("--hbm-budget", default=None,
                     help="HBM budget of the headline index (CS_FM_HBM_BUDGET: bytes, K/M/G/T suffix)")
-    ap.add_argument("--legs", default="all",
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: its roofline, the legs, the CPU baseline, p50, the "
+                         "N > 1 locate and the check of the gathered counts (off: the headline alone)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's counts to DIR/counts.npy and "
+                         "DIR/counts_summary.npy (float64, at most 64 MB; see dump_outputs)")
+    ap.add_argument("--legs", default=None,
                     help="comma-separated legs of a full N=1 run (%s), 'all' or 'none'"
                          % ",".join(ALL_LEGS))
     ap.add_argument("--legs-out", default=None,
@@ -910,14 +950,23 @@ def main():
         os.environ["CS_FM_PREFIX_K"] = str(args.prefix_k)
     if args.hbm_budget is not None:
         os.environ["CS_FM_HBM_BUDGET"] = args.hbm_budget
+    if args.only or args.legs is not None:  # asking for a leg asks for the full run's work
+        args.full = True
+    if args.legs is None:
+        args.legs = "all"
     legs = (set(ALL_LEGS) if args.legs == "all" else set() if args.legs == "none"
             else set(x for x in args.legs.split(",") if x))
     if args.only:
         legs = {args.only} - {"count"}
         args.no_cpu, args.p50_calls = True, 0
+    if not args.full:  # a plain run: the headline alone
+        legs = set()
+        args.no_cpu, args.p50_calls = True, 0
 
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     ndev = torch.cuda.device_count()  # does not initialise the GPU on this image
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher: this process starts the N ranks itself (before any GPU call)
@@ -1057,11 +1106,16 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = tt.item()
         counts = out.cpu().numpy()
+        if args.dump_outputs and rank == 0:
+            # the caller's arrays of the last timed step: the batch's counts; with the gather,
+            # every rank's shard as rank 0 received and decoded it, in pattern order
+            dump_outputs(args.dump_outputs, counts if not coll else np.concatenate(
+                [shard.unpack_counts(p, B).cpu().numpy() for p in pg.result_parts(args.steps - 1)]))
         gather_ok = None
         if coll:
             # rank 0 decodes every shard of the last step and checks it against its own
             # count of the same patterns (the whole global batch, shard by shard)
-            if rank == 0:
+            if rank == 0 and args.full:
                 gather_ok = True
                 parts = pg.result_parts((args.steps - 1))
                 for r in range(world):
@@ -1078,9 +1132,11 @@ def main():
         # launch stream) — a profile's summary is a median over as many dispatches
         # (profiles/profile_count.sh), so the two agree
         kern_avg_s = statistics.median(kern_ms) / 1e3
-        rnd, acc, frac = W.accounting(idx, info, 0, sh, dev)
+        rf = None  # the roofline takes a kernel of its own (the accounting twin): --full
+        if args.full:
+            rnd, acc, frac = W.accounting(idx, info, 0, sh, dev)
         stream_b = B * m + (B + 1) * 8 + B * 8  # patterns, offsets, uint64 counts
-        if rank == 0:
+        if rank == 0 and args.full:
             rf = roofline(rnd, stream_b, acc, kern_avg_s, B, pmc_traffic(wl, "count", kern_avg_s),
                           B * m + (B + 1) * 8,
                           (info.prefix_bytes, info.record_bytes or 8) if info.prefix_bytes
@@ -1096,6 +1152,7 @@ def main():
                        "kernel_ms_min": min(kern_ms), "kernel_ms_max": max(kern_ms),
                        "kernel_time_basis": "median of %d launches (HIP events)" % len(kern_ms),
                        "workspace_bytes": ws_bytes})
+        if rank == 0:
             res = {
                 "metric": METRIC,
                 "value": B * world * args.steps / elapsed,
@@ -1143,11 +1200,13 @@ def main():
                 "replicate_s": replicate_s,
                 "found_frac": found / B,
             }
-            if coll:
+            if rf is None:
+                del res["roofline"]
+            if coll and args.full:
                 res["gather_verified"] = gather_ok
 
     # ---- N > 1: locate of each rank's shard, positions gathered to rank 0 (gather_v) ----
-    if world > 1 and need_main and not args.only:
+    if world > 1 and need_main and args.full and not args.only:
         d_oo = torch.empty(B + 1, dtype=torch.int64, device=dev)
         cap = 2 * B
         d_pos = torch.empty(cap, dtype=torch.int64, device=dev)
@@ -1828,7 +1887,7 @@ def main():
                 res["locate"] = lg.get("locate_one") or lg["locate"]
             res["legs"] = lg
         legs_file = None
-        if args.legs_out != "none" and not args.only:
+        if args.full and args.legs_out != "none" and not args.only:
             legs_file = args.legs_out or os.path.join(
                 "gpurun_out", "bench_full_n%d_%s.json" % (world, time.strftime("%Y%m%d_%H%M%S")))
             try:
@@ -1839,7 +1898,7 @@ def main():
             except OSError as e:
                 log(rank, "could not write %s: %s" % (legs_file, e))
                 legs_file = None
-        if not args.only:
+        if args.full and not args.only:
             # the full result (every leg) on stderr as well, one line
             print("[bench] full result: " + json.dumps(res), file=sys.stderr, flush=True)
         print(compact_line(res, legs_file), flush=True)

@@ -61,7 +61,7 @@ for STEP in "$@"; do
     bench)
       C=$(cfg_args "${ARGS[0]}") || exit 1
       NAME="${NAME}_${ARGS[0]}"
-      env "${ENVS[@]}" timeout -k 10 600 python -u bench.py $C --legs-out $OUT/$NAME.full.json "${ARGS[@]:1}" > $OUT/$NAME.json 2> $OUT/$NAME.err ;;
+      env "${ENVS[@]}" timeout -k 10 600 python -u bench.py --full $C --legs-out $OUT/$NAME.full.json "${ARGS[@]:1}" > $OUT/$NAME.json 2> $OUT/$NAME.err ;;
     prof)
       C=$(cfg_args "${ARGS[0]}") || exit 1
       env "${ENVS[@]}" timeout -k 10 900 bash profiles/profile_legs.sh "${TAG}_${ARGS[0]}" "${ARGS[1]}" $C \

@@ -11,5 +11,6 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 tail -2 gpurun_out/final/pytest_gpu.log
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/final/smoke.log 2>&1 || { cat gpurun_out/final/smoke.log; exit 1; }
 tail -1 gpurun_out/final/smoke.log
-timeout -k 10 700 python -u bench.py > gpurun_out/final/bench.json 2> gpurun_out/final/bench.err || { tail -20 gpurun_out/final/bench.err; exit 1; }
+FINAL=$(ls -d "$ROOT"/*/final | head -1)  # the output directory made above
+timeout -k 10 700 python -u bench.py --full > "$FINAL/bench.json" 2> "$FINAL/bench.err" || { tail -20 "$FINAL/bench.err"; exit 1; }
 echo "bench done"

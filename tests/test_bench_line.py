@@ -64,6 +64,49 @@ def test_inflated_result_still_fits():
     assert got["value"] and got["roofline"]["frac"] and got["gather_verified"] is True
 
 
+def test_plain_result_compacts_to_the_headline():
+    # a plain run (no --full) carries no roofline, CPU baseline, p50 or legs: the line is the
+    # contract's fields, the config and the index's size
+    b = _bench()
+    full = _full()
+    res = {k: v for k, v in full.items()
+           if k not in ("roofline", "cpu_baseline", "cpu_port", "cpu_locate", "cpu_fast", "locate", "legs")
+           and not k.startswith(("p50", "p95", "p99", "max_us"))}
+    got = json.loads(b.compact_line(res, None))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "steps", "warmup", "ms_per_step",
+              "config"):
+        assert k in got, k
+    assert got["ms_per_step"] == full["ms_per_step"] and got["value"] == float("%.6g" % full["value"])
+    for k in ("roofline", "cpu_baseline", "p50_us", "locate", "legs_file"):
+        assert k not in got, k
+
+
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: float64 files; every count when they fit the cap, else the counts at a
+    fixed sample of positions; the summary covers the whole output either way."""
+    import numpy as np
+    b = _bench()
+    c = (np.arange(100_003, dtype=np.int64) * 7919) % 1000
+    c[5] = 2 ** 40 + 1  # exact in float64, not in float32
+    b.dump_outputs(str(tmp_path / "a"), c)
+    got = np.load(tmp_path / "a" / "counts.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, c.astype(np.float64))
+    s = np.load(tmp_path / "a" / "counts_summary.npy")
+    assert s.dtype == np.float64 and s.tolist() == [c.size, c.sum(), (c >= 1).sum(), c.max()]
+    # too large to write whole: the sample, identical from call to call, within the cap
+    monkeypatch.setattr(b, "DUMP_MAX_BYTES", 256 << 10)
+    monkeypatch.setattr(b, "DUMP_SAMPLE", 20_000)
+    ix = b.dump_sample_index(c.size, 20_000)
+    assert ix.size == 20_000 and int(ix.max()) < c.size and np.array_equal(ix, b.dump_sample_index(c.size, 20_000))
+    assert len(set(ix.tolist())) > 15_000  # spread over the output, not a prefix
+    b.dump_outputs(str(tmp_path / "b"), c)
+    got = np.load(tmp_path / "b" / "counts.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, c[ix.astype(np.int64)].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "b" / "counts_summary.npy"), s)
+    files = list((tmp_path / "b").iterdir())
+    assert sum(f.stat().st_size for f in files) <= 256 << 10 and all(f.suffix == ".npy" for f in files)
+
+
 def test_only_mode_keeps_the_leg_object():
     b = _bench()
     res = {"only": "count", "workload_key": "k", "count": {"frac": 0.2}, "legs": {}}
