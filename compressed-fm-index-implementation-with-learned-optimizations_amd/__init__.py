@@ -164,6 +164,7 @@ SIGNATURES = {
     "cs_fm_wt_access": (C.c_int, [_vp, _u64p, C.c_uint64, _u8p]),
     "cs_fm_lf": (C.c_int, [_vp, _u64p, C.c_uint64, _u64p]),
     "cs_fm_get_C": (C.c_int, [_vp, _u64p]),
+    "cs_fm_dna_std": (C.c_int, [_vp, _u32p]),
     "cs_fm_bwt_device": (C.c_int, [_vp, _vp, _vp]),
     "cs_fm_get_ssa": (C.c_int, [_vp, _u64p, C.c_uint64, _u64p]),
     "cs_sa_build": (C.c_int, [_u8p, C.c_uint64, _u32p, C.c_int]),
@@ -587,6 +588,13 @@ class FMIndex:
         inf = cs_fm_info()
         _check(lib().cs_fm_get_info(self._h, C.byref(inf)))
         return inf
+
+    def dna_std(self) -> bool:
+        """Whether the staged count codes this index's characters in registers, as standard
+        DNA (cs_fm_dna_std), not through the symbol map."""
+        out = np.zeros(1, np.uint32)
+        _check(lib().cs_fm_dna_std(self._h, out.ctypes.data_as(_u32p)))
+        return bool(out[0])
 
     def C(self) -> np.ndarray:
         out = np.zeros(257, np.uint64)

@@ -1444,6 +1444,15 @@ cs_status cs_fm_get_C(const cs_fm_index* h, uint64_t* out257) {
   return CS_OK;
 }
 
+cs_status cs_fm_dna_std(const cs_fm_index* h, uint32_t* out) {
+  if (!h || !out) {
+    set_error("null argument");
+    return CS_ERR_INVALID;
+  }
+  *out = h->dev().dna_std;
+  return CS_OK;
+}
+
 cs_status cs_fm_bwt_device(const cs_fm_index* h, uint8_t* d_out, void* stream) {
   DeviceScope dscope;
   cs_status s = check_handle(h, dscope);

@@ -121,12 +121,16 @@ __device__ __forceinline__ void general_rest(const DevIndex& ix, const NodeTable
                                              uint64_t* __restrict__ rec, uint64_t* kc = nullptr,
                                              uint64_t* kr = nullptr, const uint64_t* rng = nullptr) {
   uint64_t* const cnt_out = static_cast<uint64_t*>(co.out);  // kLoc
+  // (the thread's index taken afresh: shared with the stages' own s_rng address, that address
+  // stayed live from the stages to here, and the count forms spilled it on their fast path)
+  uint32_t tx = threadIdx.x;
+  asm volatile("" : "+v"(tx));
 #pragma unroll
   for (int j = 0; j < U; ++j) {
     if constexpr (!kLoc) {
       if (st[j] == 5) {  // from the range the table entry gave, m - ptab_k characters left
         const uint64_t q = q0 + (uint64_t)j * kBlk;
-        const uint64_t* r = rng + 2 * ((uint64_t)j * kBlk + threadIdx.x);
+        const uint64_t* r = rng + 2 * ((uint64_t)j * kBlk + tx);
         const uint64_t k = m[j] - ix.ptab_k;
         if constexpr (kPacked) {
           store_count<W>(co, q, count_rest<E>(ix, T, PackedDna{o0[j]}, k, r[0], r[1], nullptr, nullptr));
@@ -1330,7 +1334,13 @@ void k_count_ctx(DevIndex ix, const uint8_t* __restrict__ pats,
         cnt_out[q] = res[j] < limit ? res[j] : limit;  // fm_index.cpp:125
         rec[q] = rv[j];
       } else {
-        store_count<W>(co, q, res[j]);
+        // the output address from q0 here, inside the store's branch: formed before the
+        // branch it was kept live across (D) in two VGPRs the allocator spilled, and each
+        // count store waited for a scratch reload first (the empty asm keeps the compiler
+        // from hoisting the sum back out)
+        uint64_t qs = q0;
+        asm volatile("" : "+v"(qs));
+        store_count<W>(co, qs + (uint64_t)j * kBlk, res[j]);
       }
     }
   }

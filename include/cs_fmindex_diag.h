@@ -48,6 +48,13 @@ cs_status cs_fm_wt_rank(const cs_fm_index* h, const uint8_t* syms, const uint64_
 cs_status cs_fm_wt_access(const cs_fm_index* h, const uint64_t* pos, uint64_t k, uint8_t* out);
 cs_status cs_fm_lf(const cs_fm_index* h, const uint64_t* rows, uint64_t k, uint64_t* out);
 cs_status cs_fm_get_C(const cs_fm_index* h, uint64_t* out257);
+/* How the staged count codes this index's pattern characters (read-only): *out = 1 for
+ * occurrence lines over the standard DNA code (A C G T -> 0 1 2 3 in the table's and the
+ * occurrence alphabet, every other byte in neither), whose byte patterns are coded four
+ * characters per dword in registers; 0 for every other index (the symbol map in LDS).  A
+ * symbol is in the table's alphabet from one row in 2^20 on, so a text with a terminator is
+ * standard DNA only beyond 2^20 symbols. */
+cs_status cs_fm_dna_std(const cs_fm_index* h, uint32_t* out);
 /* The whole BWT (WaveletTree::access for every row) into device memory d_out (n
  * bytes), asynchronous on stream. */
 cs_status cs_fm_bwt_device(const cs_fm_index* h, uint8_t* d_out, void* stream);

@@ -21,7 +21,7 @@
 // the queries/s and the random-read rate.
 //
 //   hipcc -O3 --offload-arch=gfx950 mix_bench.hip -o mix_bench
-//   ./mix_bench [npat_M=12.5] [reps=21]
+//   ./mix_bench [npat_M=12.5] [reps=21] [alloc=0] [mode=0]   (mode 1: quick, 2: the oneshot_e extras)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -194,6 +194,124 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
 #pragma unroll
   for (int j = 0; j < U; ++j)
     if (live[j]) __builtin_nontemporal_store(rec_count(a[j], w[j]), out + q0 + (uint64_t)j * 256);
+}
+
+// ---- the production count's remaining extras, one switch each (U = 2, 6 waves/EU) --------
+// What k_count_ctx's routed count form does beside the access mix and the oneshot_x extras:
+// kPro:   the block prologue — every thread loads two bytes of a small table (both in flight,
+//         one wait), writes their pair to an LDS map and the block meets at a barrier before
+//         a wave's first offset load (the map is read only on a path no 20-mer takes);
+// kSpill: the output address of the lane's first pattern goes to a per-lane private (scratch)
+//         slot before the record reads and comes back from it before each of the two count
+//         stores (a local array at a runtime index behind an opaque private pointer: the round
+//         trip stays in the code object — scratch_store_dwordx2, then scratch_load_dwordx2 +
+//         s_waitcnt vmcnt(0) before each global_store_dwordx2);
+// kDummy: the pattern through nine predicated dword loads, the four past the 20-mer's five
+//         from one dummy address (load_pattern32_raw's form);
+// kKeep:  the list bookkeeping when nothing is listed — a ballot / popcount pair per pattern
+//         before the record reads (wave_list: one 4-B store of the wave's number to its slot)
+//         and one after them (the general-search number; one 4-B store of 0 to the slot).
+// `sidx` is 0 at run time (the private slot's index), `gtab` the prologue's 512-B table (and
+// the dummy address), `cnt` / `cnt2` / `list` the per-wave slot arrays.
+template <bool kPro, bool kSpill, bool kDummy, bool kKeep>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k_oneshot_e(
+    const uint4* __restrict__ tab, const uint8_t* __restrict__ pats, const uint64_t* __restrict__ offs,
+    uint64_t npat, uint64_t* __restrict__ out, const uint8_t* __restrict__ gtab, uint32_t* __restrict__ cnt,
+    uint32_t* __restrict__ cnt2, uint32_t* __restrict__ list, uint32_t sidx) {
+  constexpr int U = 2;
+  __shared__ uint16_t cmap[256];
+  if constexpr (kPro) {
+    cmap[threadIdx.x] = (uint16_t)(gtab[threadIdx.x] | (gtab[256 + threadIdx.x] << 8));
+    __syncthreads();
+  }
+  const uint64_t q0 = blockIdx.x * (uint64_t)(256 * U) + threadIdx.x;
+  uint32_t t[U], w[U];
+  bool live[U], odd[U];
+  uint64_t o[U], m[U];
+#pragma unroll
+  for (int j = 0; j < U; ++j) {
+    const uint64_t q = q0 + (uint64_t)j * 256;
+    live[j] = q < npat;
+    const uint64_t qc = live[j] ? q : npat - 1;
+    o[j] = offs[qc];
+    m[j] = offs[qc + 1] - o[j];
+  }
+  uint32_t u[U][9];
+#pragma unroll
+  for (int j = 0; j < U; ++j) {
+    const uint32_t* w0 = reinterpret_cast<const uint32_t*>(pats + o[j]);
+    if constexpr (kDummy) {
+      const uint32_t nw = live[j] ? (uint32_t)(m[j] + 3) >> 2 : 0u;
+      const uint32_t* dm = reinterpret_cast<const uint32_t*>(gtab);
+#pragma unroll
+      for (int i = 0; i < 9; ++i) u[j][i] = ((uint32_t)i < nw ? w0 : dm)[i];
+#pragma unroll
+      for (int i = 0; i < 9; ++i) u[j][i] = (uint32_t)i < nw ? u[j][i] : 0u;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 5; ++i) u[j][i] = w0[i];
+#pragma unroll
+      for (int i = 5; i < 9; ++i) u[j][i] = 0;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < U; ++j) {
+    key(u[j], t[j], w[j]);
+    w[j] |= (u[j][5] | u[j][6] | u[j][7] | u[j][8]) & 0x80000000u;  // (zero: the dwords past the pattern)
+    odd[j] = live[j] && m[j] != kM;  // none in this batch
+    if constexpr (kPro)
+      if (odd[j]) t[j] = cmap[o[j] & 255];
+  }
+  // (the private pointer through an empty asm: the compiler can neither promote the array to
+  // registers nor forward the stored value to the reload)
+  uint64_t priv[4];
+  typedef __attribute__((address_space(5))) uint64_t* priv_ptr;
+  priv_ptr pp = (priv_ptr)priv + (sidx & 3);
+  asm volatile("" : "+v"(pp));
+  if constexpr (kSpill) {
+    *pp = reinterpret_cast<uint64_t>(out + q0);
+    asm volatile("" ::: "memory");
+  }
+  const uint64_t slot = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if constexpr (kKeep) {
+    uint32_t n = 0;
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      const uint64_t bal = __ballot(odd[j]);
+      if (odd[j]) list[slot * 128 + n + __popcll(bal & ((1ull << lane) - 1ull))] = threadIdx.x + j * 256;
+      n += __popcll(bal);
+    }
+    if (lane == 0) cnt[slot] = n;
+  }
+  uint4 a[U];
+#pragma unroll
+  for (int j = 0; j < U; ++j) a[j] = ld_nt16(tab + (live[j] ? t[j] : 0u));
+  asm volatile("" ::: "memory");
+#pragma unroll
+  for (int j = 0; j < U; ++j) {
+    if (!live[j]) continue;
+    uint64_t* dst = out + q0;
+    if constexpr (kSpill) {
+      // (the reload after the record has arrived, as the production kernel's: its slot
+      // pointer passes through an asm that reads the record)
+      priv_ptr pr = pp;
+      asm volatile("" : "+v"(pr) : "v"(a[j].x) : "memory");
+      typedef __attribute__((address_space(1))) uint64_t* glob_ptr;
+      dst = (uint64_t*)(glob_ptr)(*pr);
+    }
+    __builtin_nontemporal_store(rec_count(a[j], w[j]), dst + (uint64_t)j * 256);
+  }
+  if constexpr (kKeep) {
+    uint32_t ng = 0;
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      const bool g = live[j] && (a[j].y & 15u) == 15u && a[j].z == 0xFFFFFFFFu;  // (an escaped record: none)
+      ng += (uint32_t)__popcll(__ballot(g));
+    }
+    if (ng >= 1000u) list[slot * 128] = ng;  // (never: a wave has 128 patterns)
+    else if (lane == 0) cnt2[slot] = 0;
+  }
 }
 
 // ---- the production shape's prologue: a symbol map staged in LDS from global memory --------
@@ -413,6 +531,8 @@ int main(int argc, char** argv) {
   // shapes only
   const int alloc = argc > 3 ? std::atoi(argv[3]) : 0;
   const bool quick = argc > 4 && std::atoi(argv[4]) != 0;
+  // argv[4] = 2: the plain one-shot (U = 2, 6 waves/EU) and the oneshot_e extras only
+  const bool extras = argc > 4 && std::atoi(argv[4]) == 2;
   if (alloc == 1) CK(hipExtMallocWithFlags(reinterpret_cast<void**>(&tab), kRecs * 16, hipDeviceMallocContiguous));
   else CK(hipMalloc(&tab, kRecs * 16));
   CK(hipMalloc(&pats, npat * kM + 64));
@@ -439,6 +559,34 @@ int main(int argc, char** argv) {
     std::fflush(stdout);
   };
   const unsigned g1 = (unsigned)((npat + 255) / 256);
+#define ONESHOT_E(PRO, SPILL, DUMMY, KEEP)                                                        \
+  report("oneshot_e U=2 wpe=6 prologue=" #PRO " spill_addr=" #SPILL " dummy_loads=" #DUMMY          \
+         " listkeep=" #KEEP,                                                                       \
+         median_ms(reps, [&] {                                                                     \
+           k_oneshot_e<PRO, SPILL, DUMMY, KEEP><<<g2, 256>>>(tab, pats, offs, npat, out, gtab, slots, \
+                                                             slots + g2 * 4, elist, 0u);           \
+         }),                                                                                       \
+         true)
+  if (extras) {
+    const unsigned g2 = (unsigned)((npat + 511) / 512);
+    uint8_t* gtab;
+    uint32_t *slots, *elist;
+    CK(hipMalloc(&gtab, 512));
+    CK(hipMemset(gtab, 1, 512));
+    CK(hipMalloc(&slots, (size_t)g2 * 4 * 2 * sizeof(uint32_t)));
+    CK(hipMalloc(&elist, (size_t)g2 * 4 * 128 * sizeof(uint32_t)));
+    report("oneshot U=2 wpe=6", median_ms(reps, [&] { k_oneshot<2, 6><<<g2, 256>>>(tab, pats, offs, npat, out); }),
+           true);
+    ONESHOT_E(false, false, false, false);
+    ONESHOT_E(true, false, false, false);
+    ONESHOT_E(false, true, false, false);
+    ONESHOT_E(false, false, true, false);
+    ONESHOT_E(false, false, false, true);
+    ONESHOT_E(true, true, true, true);
+    report("oneshot U=2 wpe=6 (again)",
+           median_ms(reps, [&] { k_oneshot<2, 6><<<g2, 256>>>(tab, pats, offs, npat, out); }), true);
+    return 0;
+  }
   for (unsigned g : {g1, 8u * ncu, 32u * ncu}) {
     char nm[64];
     std::snprintf(nm, sizeof nm, "rand grid=%u", g);
