@@ -3,7 +3,7 @@
 // (src/api/fm_index.cpp:107-157), as hand-written CDNA4 kernels.
 //
 // Every kernel is a template over a rank ENGINE (occ(c, i) for a search step, and
-// LF with the BWT symbol), dispatched on the index's format (FMX_DISPATCH):
+// LF with the BWT symbol), dispatched on the index's format (with_engine, fm_search.hpp):
 //   OccE        occurrence lines: one 32-B line per rank of any symbol (<= 4
 //               frequent symbols, rare rows listed in the node table);
 //   QWM         quaternary wavelet matrix of occurrence lines: one line per base-4
@@ -28,7 +28,7 @@
 namespace fmx {
 namespace {
 
-// offs == nullptr: patterns of one length fixed_m at stride fixed_m (cs_fm_count_fixed_device);
+// offs == nullptr: patterns of one length fixed_m at stride fixed_m (cs_fm_count_device with d_offs = NULL);
 // kPacked: pats holds one uint64 per pattern, fixed_m <= 32 2-bit DNA characters (PackedDna);
 // kLA: long patterns (launch_count_ex, CS_Q_LONG), the text comparison with look-ahead
 template <class E, bool kPacked, bool kLA = false>
@@ -2969,6 +2969,56 @@ __global__ __launch_bounds__(kBlk) void k_locate_one_gen(DevIndex ix, const uint
   locate_split_store<U, 0>(ix, T, npat, blockIdx.x, q0, kc, kr, op);
 }
 
+}  // namespace
+
+// Phase 2 with the full suffix array, fused (no rows buffer): each pattern's rows come
+// from its record (as k_expand_rows) and go straight through SA: SA[row] - k (mod n) for
+// a window row k characters before the end, SA[row] otherwise.  A lane
+// takes a pattern of at most kLocSmall rows (every context window: <= kLocSpanBits);
+// wider plain ranges are listed for k_locate_sa_wide, a block per range.
+__global__ __launch_bounds__(kBlk) void k_locate_sa(const uint32_t* __restrict__ sa, uint64_t n,
+                                                    const uint64_t* __restrict__ sp,
+                                                    const uint64_t* __restrict__ offs, uint64_t npat,
+                                                    uint64_t* __restrict__ out,
+                                                    uint64_t* __restrict__ wide,
+                                                    unsigned long long* __restrict__ nwide) {
+  const uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t q = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; q < npat; q += gs) {
+    const uint64_t a = offs[q], c = offs[q + 1] - a, s = sp[q];
+    if (!c) continue;
+    if (s & kLocCtx) {
+      uint64_t r0, adj;
+      uint32_t rel;
+      loc_window(s, r0, adj, rel);
+      for (uint64_t j = 0; j < c; ++j) {
+        const uint32_t f = (uint32_t)__ffs(rel) - 1u;
+        const uint64_t p = load_sa(sa, r0 + f);
+        st_out(out + a + j, p >= adj ? p - adj : p + n - adj);
+        rel &= rel - 1u;
+      }
+    } else if (c <= kLocSmall) {
+      for (uint64_t j = 0; j < c; ++j) st_out(out + a + j, (uint64_t)sa[s + j]);
+    } else {
+      wide[atomicAdd(nwide, 1ull)] = q;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kBlk) void k_locate_sa_wide(const uint32_t* __restrict__ sa,
+                                                         const uint64_t* __restrict__ sp,
+                                                         const uint64_t* __restrict__ offs,
+                                                         uint64_t* __restrict__ out,
+                                                         const uint64_t* __restrict__ wide,
+                                                         const unsigned long long* __restrict__ nwide) {
+  const uint64_t nw = *nwide;
+  for (uint64_t e = blockIdx.x; e < nw; e += gridDim.x) {
+    const uint64_t q = wide[e], a = offs[q], c = offs[q + 1] - a, s = sp[q];
+    for (uint64_t j = threadIdx.x; j < c; j += blockDim.x) st_out(out + a + j, (uint64_t)sa[s + j]);
+  }
+}
+
+namespace {  // (the two kernels above keep their external names)
+
 // The reported rows of pattern q in row order (fm_index.cpp:125): sp[q] + (j -
 // offs[q]) for a plain record, else the window's matching rows, tagged with k.
 __global__ void k_expand_rows(const uint64_t* __restrict__ sp, const uint64_t* __restrict__ offs,
@@ -3606,13 +3656,21 @@ cs_status launch_extract(const cs_fm_index* h, const uint64_t* d_pos, const uint
     FMX_HIP(hipGetLastError());
     return CS_OK;
   }
-  FMX_DISPATCH(h, k_extract, grid_for(k, kBlk, 0xFFFFFFFFu), h->dev(), d_pos, d_len, d_out_offs, k,
-               d_out);
+  with_engine(h->line_fmt, [&](auto engine) {
+    using E = typename decltype(engine)::type;
+    k_extract<E><<<grid_for(k, kBlk, 0xFFFFFFFFu), kBlk, 0, st>>>(h->dev(), d_pos, d_len, d_out_offs,
+                                                                  k, d_out);
+  });
+  FMX_HIP(hipGetLastError());
   return CS_OK;
 }
 
 cs_status launch_bwt(const cs_fm_index* h, uint8_t* d_out, hipStream_t st) {
-  FMX_DISPATCH(h, k_bwt, grid_for(h->n, kBlk, 65536), h->dev(), d_out);
+  with_engine(h->line_fmt, [&](auto engine) {
+    using E = typename decltype(engine)::type;
+    k_bwt<E><<<grid_for(h->n, kBlk, 65536), kBlk, 0, st>>>(h->dev(), d_out);
+  });
+  FMX_HIP(hipGetLastError());
   return CS_OK;
 }
 
@@ -3667,9 +3725,6 @@ inline bool qctx_staged(uint32_t flags) { return !(flags & CS_QT_QCTX_UNSTAGED);
 // the call's flags with the handle's tuning defaults
 inline uint32_t call_flags(const cs_fm_index* h, uint32_t flags) { return flags | h->tune; }
 
-// k_count_long over the batch (skip_short: only its long patterns, as k_count_ctx's kSkipLong),
-// then k_count_list over the patterns it listed; byte_text: the byte text even when the
-// index has the packed one (tuning hook CS_FM_LONG_KERNEL=2)
 // The call's long-pattern lists (LongList): the counters' header (kListHdrBytes, zero between
 // calls), slot lists of the staged kernel (list / cnt, unless `direct`) and of k_count_long /
 // k_locate_long for the general search (list2 / cnt2), offsets inside the slots' regions (u16; list2 u32 with the chain);
@@ -3679,35 +3734,44 @@ inline uint32_t call_flags(const cs_fm_index* h, uint32_t flags) { return flags 
 // otherwise the staged kernel writes every slot's counts, wave by wave.
 static_assert(kLongRegion == 2 * kBlk && kLongSlot == 2 * 64, "a slot is one wave's patterns (U = 2)");
 static_assert(kListHdrBytes % 256 == 0, "the lists start 256-B aligned");
+// Where each part sits (byte offsets from the header's start) and the total: the one
+// description LongBufs::bytes and LongBufs::alloc share.  Unless direct, list, cnt and rng2
+// are there too; direct, their offsets coincide with the next part's.
+struct LongLayout {
+  uint64_t slots, entries;  // the batch's slots; list entries (kLongSlot per slot)
+  uint64_t list2, list, cnt2, cnt, rng2, bytes;
+  LongLayout(uint64_t npat, bool direct) {
+    slots = (npat + kLongRegion - 1) / kLongRegion * kSlotsPerRegion;
+    entries = slots * kLongSlot;
+    list2 = kListHdrBytes;                      // u32 entries
+    list = list2 + entries * 4;                 // u16 entries
+    cnt2 = list + (direct ? 0 : entries * 2);   // u32 per slot
+    cnt = cnt2 + slots * 4;                     // u32 per slot
+    rng2 = cnt + (direct ? 0 : slots * 4);      // the general-search entries' ranges, 8 B each
+    bytes = rng2 + (direct ? 0 : entries * 8);  // (rng2 8-B aligned: slots % 4 == 0)
+  }
+};
 struct LongBufs {
   StreamBuf buf;
   LongList ll;
-  static uint64_t bytes(uint64_t npat, bool direct) {
-    const uint64_t slots = (npat + kLongRegion - 1) / kLongRegion * kSlotsPerRegion;
-    // list2 (u32 entries) and cnt2; unless direct, list (u16), cnt and the ranges of the
-    // general-search entries (8 B each)
-    return kListHdrBytes + slots * (kLongSlot * 4 + 4) + (direct ? 0 : slots * (kLongSlot * (2 + 8) + 4));
-  }
+  static uint64_t bytes(uint64_t npat, bool direct) { return LongLayout(npat, direct).bytes; }
   // into `at` (bytes(npat, direct) of it: the caller's workspace, whose header the calls keep
   // zeroed, or the call's own allocation when `fresh`), or an allocation of its own
   cs_status alloc(uint64_t npat, bool direct, hipStream_t st, void* at = nullptr, bool fresh = true) {
-    const uint64_t regions = (npat + kLongRegion - 1) / kLongRegion, slots = regions * kSlotsPerRegion;
-    const uint64_t entries = slots * kLongSlot;
-    const uint64_t lists = entries * 4 + (direct ? 0 : entries * 2);
-    if (!at) FMX_HIP(buf.alloc(bytes(npat, direct), st));
+    const LongLayout L(npat, direct);
+    if (!at) FMX_HIP(buf.alloc(L.bytes, st));
     uint8_t* p = at ? static_cast<uint8_t*>(at) : buf.as<uint8_t>();
-    ll.hdr = reinterpret_cast<uint32_t*>(p);
-    if ((!at || fresh) && !direct) FMX_HIP(hipMemsetAsync(p, 0, kListHdrBytes, st));
-    p += kListHdrBytes;
-    ll.list2 = reinterpret_cast<uint32_t*>(p);
-    ll.cnt2 = reinterpret_cast<uint32_t*>(p + lists);
+    ll.list2 = reinterpret_cast<uint32_t*>(p + L.list2);
+    ll.cnt2 = reinterpret_cast<uint32_t*>(p + L.cnt2);
     if (!direct) {
-      ll.list = reinterpret_cast<uint16_t*>(p + entries * 4);
-      ll.cnt = ll.cnt2 + slots;
-      ll.rng2 = reinterpret_cast<uint64_t*>(p + lists + 2 * slots * 4);  // (8-B aligned: slots % 4 == 0)
+      ll.hdr = reinterpret_cast<uint32_t*>(p);
+      if (!at || fresh) FMX_HIP(hipMemsetAsync(p, 0, kListHdrBytes, st));
+      ll.list = reinterpret_cast<uint16_t*>(p + L.list);
+      ll.cnt = reinterpret_cast<uint32_t*>(p + L.cnt);
+      ll.rng2 = reinterpret_cast<uint64_t*>(p + L.rng2);
     } else {
       ll.hdr = nullptr;
-      FMX_HIP(hipMemsetAsync(ll.cnt2, 0, slots * 4, st));
+      FMX_HIP(hipMemsetAsync(ll.cnt2, 0, L.slots * 4, st));
     }
     return CS_OK;
   }
@@ -3744,14 +3808,14 @@ unsigned long_list_grid(uint64_t npat, uint32_t want = kLongListGrid) {
   return (unsigned)std::max<uint64_t>(g, 1);
 }
 
-// k_count_long over the batch (from_list: the staged kernel's lists in ll), then k_count_list
-// over what it could not finish.  skip_short (twin): every pattern read, only the long ones
-// searched.
 // whether k_count_long verifies long patterns at their walks' positions (round 6): the
 // index keeps no full SA (DevIndex::vsa) but walk lines and a text to compare against
 inline bool walk_verify(const DevIndex& ix) {
   return !ix.vsa && ix.walk && ix.wssa && ix.lf_exact && (ix.wtext || (ix.ptext && ix.wrare));
 }
+// k_count_long over the batch (routed: the staged kernel's lists), then, unless routed,
+// k_count_list over the patterns it listed.  skip_short (the twin, as k_count_ctx's
+// kSkipLong): every pattern read, only the long ones searched.
 template <bool kBytes>
 cs_status launch_count_long_t(const DevIndex& ix, const uint8_t* d_pats, const uint64_t* d_offs,
                               uint64_t npat, const CountOut& co, hipStream_t st, uint64_t fixed_m,
@@ -3765,51 +3829,34 @@ cs_status launch_count_long_t(const DevIndex& ix, const uint8_t* d_pats, const u
     if (s != CS_OK) return s;
     ll = own.ll;
   }
-  const unsigned g = routed ? long_list_grid(npat, routed->grid) : grid_for(npat, kBlk, 0xFFFFFFFFu);
-  // CS_QT_LONG_LOADS8 (CS_FM_LONG_V16=0): 8-B pattern / window loads; the default 16-B vectors
-  // for the pattern's packed part and the window (C4 150-mers 1.87 -> 1.55 ms, 64-mers 1.25 ->
-  // 1.16-1.21, profiles/r03/long_probe_v16.json; round 4's partial forms 1 / 2 are gone)
+  // walk: candidates positioned by their short walks (round 6; the index keeps no full SA),
+  // over narrow (1) or wide (2) walk lines; 0: positions from the full SA
   const int walk = walk_verify(ix) ? (ix.wide ? 2 : 1) : 0;
-  if (walk && kBytes) {  // the measurement twin of the walk forms (direct launches only)
-    if (walk == 2 && ix.ptext)
-      k_count_long<0, true, true, 3, false, 2><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m, ll, skip_short);
-    else if (walk == 2)
-      k_count_long<0, false, true, 0, false, 2><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m, ll, skip_short);
-    else if (ix.ptext)
-      k_count_long<0, true, true, 3, false, 1><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m, ll, skip_short);
-    else
-      k_count_long<0, false, true, 0, false, 1><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m, ll, skip_short);
-  } else if (walk) {  // (round 6) candidates positioned by their short walks (no full SA)
-    // against the 2-bit text when the index has it (C5), else the byte text
-    const bool pt = ix.ptext != nullptr && !byte_text;
-    if (routed && walk == 2 && pt)
-      k_count_long<0, true, false, 3, true, 2><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m, ll, false);
-    else if (routed && walk == 2)
-      k_count_long<0, false, false, 0, true, 2><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m, ll, false);
-    else if (routed && pt)
-      k_count_long<0, true, false, 3, true, 1><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m, ll, false);
-    else if (routed)
-      k_count_long<0, false, false, 0, true, 1><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m, ll, false);
-    else if (walk == 2 && pt)
-      k_count_long<0, true, false, 3, false, 2><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m, ll, skip_short);
-    else if (walk == 2)
-      k_count_long<0, false, false, 0, false, 2><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m, ll, skip_short);
-    else if (pt)
-      k_count_long<0, true, false, 3, false, 1><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m, ll, skip_short);
-    else
-      k_count_long<0, false, false, 0, false, 1><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m, ll, skip_short);
-  } else if (routed && ix.ptext && !byte_text && !loads8)  // the routed default
-    k_count_long<0, true, kBytes, 3, true><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m, ll, false);
-  else if (routed && ix.ptext && !byte_text)
-    k_count_long<0, true, kBytes, 0, true><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m, ll, false);
-  else if (routed)
-    k_count_long<0, false, kBytes, 0, true><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m, ll, false);
-  else if (ix.ptext && !byte_text && !loads8)
-    k_count_long<0, true, kBytes, 3><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m, ll, skip_short);
-  else if (ix.ptext && !byte_text)
-    k_count_long<0, true, kBytes><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m, ll, skip_short);
-  else
-    k_count_long<0, false, kBytes><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m, ll, skip_short);
+  // the measurement twin of the walk forms: direct launches only, and it reads no selector
+  const bool walk_twin = walk && kBytes;
+  // list: the routed form (the staged kernel's lists, then the search of what it lists itself)
+  const bool list = routed && !walk_twin;
+  // pt: against the 2-bit text when the index has it (C5), else the byte text;
+  // CS_QT_LONG_BYTE_TEXT (CS_FM_LONG_KERNEL=2): the byte text even so
+  const bool pt = ix.ptext != nullptr && (walk_twin || !byte_text);
+  // v16: 16-B vectors for the pattern's packed part and the window, the default with the
+  // 2-bit text (C4 150-mers 1.87 -> 1.55 ms, 64-mers 1.25 -> 1.16-1.21,
+  // profiles/r03/long_probe_v16.json; round 4's partial forms 1 / 2 are gone);
+  // CS_QT_LONG_LOADS8 (CS_FM_LONG_V16=0): 8-B loads, which the walk forms ignore
+  const int v16 = pt && (walk || !loads8) ? 3 : 0;
+  const unsigned g = routed ? long_list_grid(npat, routed->grid) : grid_for(npat, kBlk, 0xFFFFFFFFu);
+  with_int<0, 1, 2>(walk, [&](auto kWalk) {
+    with_bool(pt, [&](auto kPT) {
+      with_int<3, 0>(v16, [&](auto kV16) {
+        with_bool(list, [&](auto kList) {
+          // the forms the choices above can make
+          if constexpr ((kPT ? kV16 == 3 || kWalk == 0 : kV16 == 0) && !(kList && kWalk && kBytes))
+            k_count_long<0, kPT, kBytes, kV16, kList, kWalk><<<g, kBlk, 0, st>>>(
+                ix, d_pats, d_offs, npat, co, fixed_m, ll, kList ? false : skip_short);
+        });
+      });
+    });
+  });
   FMX_HIP(hipGetLastError());
   if (!routed) {  // (a routed k_count_long searches what it listed itself)
     k_count_list<0, kBytes><<<long_list_grid(npat), kBlk, 0, st>>>(
@@ -3849,40 +3896,23 @@ cs_status launch_count_staged(const cs_fm_index* h, const DevIndex& ix, const ui
                               const uint64_t* d_offs, uint64_t npat, const CountOut& co,
                               hipStream_t st, uint64_t fixed_m, bool packed, uint32_t flags,
                               const Work& work) {
-  // patterns per lane: CS_QT_COUNT_U1 / CS_QT_COUNT_U4 (CS_FM_COUNT_U=1 / 4), else 2
-  const int U = (flags & CS_QT_COUNT_U1) ? 1 : (flags & CS_QT_COUNT_U4) ? 4 : 2;
-  const bool nobar = count_nobar(flags);
-  const bool lo = h->line_fmt == kFmtLOcc;
-  const unsigned g2 = grid_for((npat + 1) / 2, kBlk, 0xFFFFFFFFu);
-  if (packed && lo && nobar)
-    k_count_ctx<LOccE, 2, false, true, W, true><<<g2, kBlk, 0, st>>>(ix, d_pats, nullptr, npat, co, 0,
-                                                                      nullptr, fixed_m);
-  else if (packed && lo)
-    k_count_ctx<LOccE, 2, false, true, W><<<g2, kBlk, 0, st>>>(ix, d_pats, nullptr, npat, co, 0,
-                                                                nullptr, fixed_m);
-  else if (packed && nobar)
-    k_count_ctx<OccE, 2, false, true, W, true><<<g2, kBlk, 0, st>>>(ix, d_pats, nullptr, npat, co, 0,
-                                                                     nullptr, fixed_m);
-  else if (packed)
-    k_count_ctx<OccE, 2, false, true, W><<<g2, kBlk, 0, st>>>(ix, d_pats, nullptr, npat, co, 0,
-                                                               nullptr, fixed_m);
-  else if (lo && nobar)
-    k_count_ctx<LOccE, 2, false, false, W, true><<<g2, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, 0,
-                                                                       nullptr, fixed_m);
-  else if (lo)
-    k_count_ctx<LOccE, 2, false, false, W><<<g2, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, 0,
-                                                                 nullptr, fixed_m);
-  else if (W == 8 && U == 1)
-    k_count_ctx<OccE, 1, false, false, 8><<<grid_for(npat, kBlk, 0xFFFFFFFFu), kBlk, 0, st>>>(
-        ix, d_pats, d_offs, npat, co, 0, nullptr, fixed_m);
-  else if (W == 8 && U == 4)
-    k_count_ctx<OccE, 4, false, false, 8><<<grid_for((npat + 3) / 4, kBlk, 0xFFFFFFFFu), kBlk, 0, st>>>(
-        ix, d_pats, d_offs, npat, co, 0, nullptr, fixed_m);
-  else if (d_offs && can_route(h, ix, flags)) {
+  // learned: learned occurrence lines (LOccE), else occurrence lines (OccE)
+  const bool learned = h->line_fmt == kFmtLOcc;
+  // U, patterns per lane: 2.  CS_QT_COUNT_U1 / CS_QT_COUNT_U4 (CS_FM_COUNT_U=1 / 4) have forms
+  // only at width 8 over byte strings on occurrence lines; every other call ignores them.
+  const bool plain = !packed && !learned;
+  const int U = !(W == 8 && plain) ? 2 : (flags & CS_QT_COUNT_U1) ? 1 : (flags & CS_QT_COUNT_U4) ? 4 : 2;
+  // nobar: the default, CS_QT_BARRIER turns it off (count_nobar above); the U = 1 / 4 forms
+  // keep the barrier whatever the flag says
+  const bool nobar = U == 2 && count_nobar(flags);
+  // routed: can_route (above) for byte strings with offsets at U = 2; packed batches and
+  // learned lines never route
+  const bool routed = U == 2 && plain && d_offs && can_route(h, ix, flags);
+  LongBufs lb;
+  if (routed) {
     // routing inside the call: the staged kernel counts what its one read answers and lists
     // the long patterns and (unless CS_QT_GENERAL_INLANE) the general-search ones;
     // k_count_long takes both lists from the workspace (or the call's allocation)
-    LongBufs lb;
     const bool ws = work.p && work.bytes >= LongBufs::bytes(npat, false);
     cs_status s = lb.alloc(npat, false, st, ws ? work.p : nullptr, false);
     if (s != CS_OK) return s;
@@ -3894,22 +3924,27 @@ cs_status launch_count_staged(const cs_fm_index* h, const DevIndex& ix, const ui
     lb.ll.gen_list = (flags & CS_QT_GENERAL_INLANE) ? 0u : (flags & CS_QT_GENERAL_LIST_ALL) ? 1u
                      : ix.vsa ? h->gen_list_min : 0u;
     lb.ll.grid = h->list_grid;
-    if (nobar)
-      k_count_ctx<OccE, 2, false, false, W, true, false, true><<<g2, kBlk, 0, st>>>(
-          ix, d_pats, d_offs, npat, co, 0, nullptr, fixed_m, OnePass{}, lb.ll);
-    else
-      k_count_ctx<OccE, 2, false, false, W, false, false, true><<<g2, kBlk, 0, st>>>(
-          ix, d_pats, d_offs, npat, co, 0, nullptr, fixed_m, OnePass{}, lb.ll);
-    FMX_HIP(hipGetLastError());
-    return launch_count_long(ix, d_pats, d_offs, npat, co, st, fixed_m, &lb.ll, flags);
-  } else if (nobar)
-    k_count_ctx<OccE, 2, false, false, W, true><<<g2, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, 0,
-                                                                      nullptr, fixed_m);
-  else
-    k_count_ctx<OccE, 2, false, false, W><<<g2, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, 0,
-                                                                nullptr, fixed_m);
+  }
+  const unsigned g = grid_for((npat + U - 1) / U, kBlk, 0xFFFFFFFFu);
+  with_bool(learned, [&](auto kLearned) {
+    with_int<2, 1, 4>(U, [&](auto kU) {
+      with_bool(packed, [&](auto kPacked) {
+        with_bool(nobar, [&](auto kNoBar) {
+          with_bool(routed, [&](auto kSkipLong) {
+            using E = std::conditional_t<kLearned, LOccE, OccE>;
+            constexpr bool kLoc = false, kOne = false, kPlain = !kPacked && !kLearned;
+            // the forms the choices above can make
+            if constexpr (kU == 2 ? kPlain || !kSkipLong : W == 8 && kPlain && !kNoBar && !kSkipLong)
+              k_count_ctx<E, kU, kLoc, kPacked, W, kNoBar, kOne, kSkipLong><<<g, kBlk, 0, st>>>(
+                  ix, d_pats, kPacked ? nullptr : d_offs, npat, co, /*limit*/ 0, /*rec*/ nullptr,
+                  fixed_m, OnePass{}, kSkipLong ? lb.ll : LongList{});
+          });
+        });
+      });
+    });
+  });
   FMX_HIP(hipGetLastError());
-  return CS_OK;
+  return routed ? launch_count_long(ix, d_pats, d_offs, npat, co, st, fixed_m, &lb.ll, flags) : CS_OK;
 }
 
 uint64_t count_workspace_bytes(const cs_fm_index* h, uint64_t npat) {
@@ -3923,61 +3958,64 @@ cs_status launch_count_ex(const cs_fm_index* h, const uint8_t* d_pats, const uin
   if (!npat) return CS_OK;
   flags = call_flags(h, flags);
   const DevIndex ix = query_dev(h, flags);
-  if (h->line_fmt == kFmtQwm && ix.ptab_k && ix.lctx && !ix.wide && !packed && qctx_staged(flags)) {
-    // the staged quaternary-matrix kernel (C3)
-    const unsigned g2 = grid_for((npat + 1) / 2, kBlk, 0xFFFFFFFFu);
-    if (co.width == 8)
-      k_count_qctx<2, 8><<<g2, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m);
-    else if (co.width == 4)
-      k_count_qctx<2, 4><<<g2, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m);
-    else
-      k_count_qctx<2, 1><<<g2, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m);
-    FMX_HIP(hipGetLastError());
-    return CS_OK;
-  }
-  if (h->line_fmt == kFmtOcc && ix.ptab_k && (ix.vsa || walk_verify(ix)) && !packed &&
-      ((flags & CS_Q_LONG) || (!d_offs && fixed_m > kLongPatternM))) {
-    // long patterns: one per lane in k_count_long (record, candidates, SA, text window as
-    // independent rounds; against the 2-bit text when the index has it), the patterns it
-    // does not answer listed for k_count_list; kept out of the staged kernel, whose
-    // registers the pattern and text words would take from the 20-mer path.
-    // CS_QT_LONG_ROUND2 (CS_FM_LONG_KERNEL=0): round 2's kernel (the general search with
-    // look-ahead rounds, k_count<OccE, false, true>); CS_QT_LONG_BYTE_TEXT (=2): the byte text
-    // even when the packed text is there.
-    if (flags & CS_QT_LONG_ROUND2) {
-      k_count<OccE, false, true><<<grid_for(npat, kBlk, 0xFFFFFFFFu), kBlk, 0, st>>>(ix, d_pats, d_offs,
-                                                                                    npat, co, fixed_m);
-    } else {
-      cs_status r = launch_count_long(ix, d_pats, d_offs, npat, co, st, fixed_m, nullptr, flags);
-      if (r != CS_OK) return r;
-    }
-    FMX_HIP(hipGetLastError());
-    return CS_OK;
-  }
-  if ((h->line_fmt == kFmtOcc || h->line_fmt == kFmtLOcc) && ix.ptab_k) {
-    if (co.width == 8) return launch_count_staged<8>(h, ix, d_pats, d_offs, npat, co, st, fixed_m, packed, flags, work);
-    if (co.width == 4) return launch_count_staged<4>(h, ix, d_pats, d_offs, npat, co, st, fixed_m, packed, flags, work);
-    return launch_count_staged<1>(h, ix, d_pats, d_offs, npat, co, st, fixed_m, packed, flags, work);
-  }
+  // qctx: the staged quaternary-matrix kernel (C3) — a narrow index with prefix table and
+  // contexts, byte strings, unless CS_QT_QCTX_UNSTAGED
+  const bool qctx = h->line_fmt == kFmtQwm && ix.ptab_k && ix.lctx && !ix.wide && !packed && qctx_staged(flags);
+  // long_batch: long patterns, one per lane in k_count_long (record, candidates, SA, text
+  // window as independent rounds; against the 2-bit text when the index has it), the patterns
+  // it does not answer listed for k_count_list; kept out of the staged kernel, whose
+  // registers the pattern and text words would take from the 20-mer path.  A CS_Q_LONG batch
+  // or fixed-length patterns past kLongPatternM, on the indexes k_count_long serves.
+  const bool long_batch = h->line_fmt == kFmtOcc && ix.ptab_k && (ix.vsa || walk_verify(ix)) && !packed &&
+                          ((flags & CS_Q_LONG) || (!d_offs && fixed_m > kLongPatternM));
+  // staged: k_count_ctx, occurrence lines (learned or not) with a prefix table
+  const bool staged = (h->line_fmt == kFmtOcc || h->line_fmt == kFmtLOcc) && ix.ptab_k;
   const unsigned g = grid_for(npat, kBlk, 0xFFFFFFFFu);
-  if (packed)
-    FMX_DISPATCH2(h, k_count, true, g, ix, d_pats, nullptr, npat, co, fixed_m);
-  else
-    FMX_DISPATCH2(h, k_count, false, g, ix, d_pats, d_offs, npat, co, fixed_m);
+  if (qctx) {
+    const unsigned g2 = grid_for((npat + 1) / 2, kBlk, 0xFFFFFFFFu);
+    with_int<8, 4, 1>(co.width, [&](auto W) {
+      k_count_qctx<2, W><<<g2, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m);
+    });
+  } else if (long_batch && (flags & CS_QT_LONG_ROUND2)) {
+    // CS_QT_LONG_ROUND2 (CS_FM_LONG_KERNEL=0): round 2's kernel, the general search with
+    // look-ahead rounds
+    k_count<OccE, false, true><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, fixed_m);
+  } else if (long_batch) {
+    return launch_count_long(ix, d_pats, d_offs, npat, co, st, fixed_m, nullptr, flags);
+  } else if (staged) {
+    return with_int<8, 4, 1>(co.width, [&](auto W) {
+      return launch_count_staged<W>(h, ix, d_pats, d_offs, npat, co, st, fixed_m, packed, flags, work);
+    });
+  } else {  // the general search, one pattern per lane, on any engine
+    with_engine(h->line_fmt, [&](auto engine) {
+      with_bool(packed, [&](auto kPacked) {
+        using E = typename decltype(engine)::type;
+        k_count<E, kPacked><<<g, kBlk, 0, st>>>(ix, d_pats, kPacked ? nullptr : d_offs, npat, co, fixed_m);
+      });
+    });
+  }
+  FMX_HIP(hipGetLastError());
   return CS_OK;
 }
 
 cs_status launch_count_one(const cs_fm_index* h, const OnePattern& p, uint64_t* out_host,
                            hipStream_t st) {
-  FMX_DISPATCH1(h, k_count_one, h->dev(), p, out_host);
+  with_engine(h->line_fmt, [&](auto engine) {
+    using E = typename decltype(engine)::type;
+    k_count_one<E><<<1, 64, 0, st>>>(h->dev(), p, out_host);
+  });
+  FMX_HIP(hipGetLastError());
   return CS_OK;
 }
 
 cs_status launch_count_server(const cs_fm_index* h, uint32_t seq_done, uint64_t idle_ticks,
                               uint64_t life_ticks) {
-  hipStream_t st = h->server.st;
-  FMX_DISPATCH1(h, k_count_server, h->dev(), h->server.mbox, h->server.resp, seq_done, idle_ticks,
-                life_ticks);
+  with_engine(h->line_fmt, [&](auto engine) {
+    using E = typename decltype(engine)::type;
+    k_count_server<E><<<1, 64, 0, h->server.st>>>(h->dev(), h->server.mbox, h->server.resp, seq_done,
+                                                  idle_ticks, life_ticks);
+  });
+  FMX_HIP(hipGetLastError());
   return CS_OK;
 }
 
@@ -3988,14 +4026,23 @@ cs_status launch_count_bytes(const cs_fm_index* h, const uint8_t* d_pats, const 
   const DevIndex ix = query_dev(h, flags);
   // the patterns k_count_long counts (CS_Q_LONG: all of them; routed device batches: those
   // of kFastM characters or more) take its twin, the rest the general search's
-  const bool lk = h->line_fmt == kFmtOcc && ix.ptab_k && (ix.vsa || walk_verify(ix));
-  const bool old = (flags & CS_QT_LONG_ROUND2) != 0;
-  if (!(lk && (flags & CS_Q_LONG) && !old))
-    FMX_DISPATCH(h, k_count_bytes, grid_for(npat, kBlk, 0xFFFFFFFFu), ix, d_pats, d_offs, npat, d_out);
-  // (a routed call's long patterns: can_route; ADVICE r03: the twin now follows the call)
-  if (lk && !old && ((flags & CS_Q_LONG) || (d_offs && can_route(h, ix, flags)))) {
+  // lk: the index is one k_count_long serves, and the call does not ask for round 2's kernel
+  const bool lk = h->line_fmt == kFmtOcc && ix.ptab_k && (ix.vsa || walk_verify(ix)) &&
+                  !(flags & CS_QT_LONG_ROUND2);
+  // all_long: a CS_Q_LONG batch, every pattern to the twin
+  const bool all_long = lk && (flags & CS_Q_LONG);
+  // some_long: a routed call's long patterns (can_route; ADVICE r03: the twin follows the call)
+  const bool some_long = lk && !all_long && d_offs && can_route(h, ix, flags);
+  if (!all_long) {
+    with_engine(h->line_fmt, [&](auto engine) {
+      using E = typename decltype(engine)::type;
+      k_count_bytes<E><<<grid_for(npat, kBlk, 0xFFFFFFFFu), kBlk, 0, st>>>(ix, d_pats, d_offs, npat, d_out);
+    });
+    FMX_HIP(hipGetLastError());
+  }
+  if (all_long || some_long) {
     const CountOut co{d_out, nullptr, nullptr, 0, 8};
-    return launch_count_long_t<true>(ix, d_pats, d_offs, npat, co, st, 0, nullptr, !(flags & CS_Q_LONG),
+    return launch_count_long_t<true>(ix, d_pats, d_offs, npat, co, st, 0, nullptr, /*skip_short*/ !all_long,
                                      (flags & CS_QT_LONG_BYTE_TEXT) != 0, (flags & CS_QT_LONG_LOADS8) != 0);
   }
   return CS_OK;
@@ -4020,15 +4067,32 @@ cs_status launch_locrec_hits(const cs_fm_index* h, const uint8_t* d_pats, const 
 // stream-ordered allocation.
 // (+ on walk-line indexes the walk list: kLocTile (output index, row) pairs per tile and the
 // tiles' counts)
+// Where each part sits (byte offsets from the buffers' start, after the lists) and the total:
+// the one description the workspace sizes and launch_locate_onepass's pointers share.
+struct LocateLayout {
+  uint64_t ntiles;  // tiles of kLocTile patterns
+  uint64_t rec, tiles, nwide, wide, counts, wcnt, walks, sflags, bytes;
+  LocateLayout(const cs_fm_index* h, uint64_t npat, uint64_t wide_cap) {
+    ntiles = (npat + kLocTile - 1) / kLocTile;
+    const uint64_t cb = h->wide ? 8 : 4;  // count bytes (a wide index's counts pass 2^32)
+    const bool walk = !h->d_sa;           // a walk-line index: the walk list
+    rec = 0;                                              // a record per pattern, 8 B
+    tiles = rec + npat * 8;                               // a total per tile, 8 B
+    nwide = tiles + ntiles * 8;                           // the wide ranges' counter, 8 B
+    wide = nwide + 8;                                     // wide_cap wide ranges, 16 B each
+    counts = wide + wide_cap * 16;                        // a count per pattern, cb bytes
+    wcnt = counts + ((npat * cb + 7) & ~7ull);            // the tiles' walk counts, u32
+    walks = wcnt + (walk ? (ntiles * 4 + 7) & ~7ull : 0);  // kLocTile 16-B walk slots per tile
+    sflags = walks + (walk ? ntiles * kLocTile * 16 : 0);  // the chained scan's flags and ticket
+    bytes = sflags + (kScanMaxBlocks + 1) * 8;
+  }
+};
 uint64_t locate_walk_bytes(const cs_fm_index* h, uint64_t npat) {
-  const uint64_t tiles = (npat + kLocTile - 1) / kLocTile;
-  return h->d_sa ? 0 : ((tiles * 4 + 7) & ~7ull) + tiles * kLocTile * 16;
+  const LocateLayout L(h, npat, npat);
+  return L.sflags - L.wcnt;
 }
 uint64_t locate_lo_bytes(const cs_fm_index* h, uint64_t npat, uint64_t wide_cap) {
-  const uint64_t tiles = (npat + kLocTile - 1) / kLocTile;
-  const uint64_t cb = h->wide ? 8 : 4;  // count bytes (a wide index's counts pass 2^32)
-  return ((npat * (8 + cb) + tiles * 8 + 8 + wide_cap * 16 + 7) & ~7ull) + locate_walk_bytes(h, npat) +
-         (kScanMaxBlocks + 1) * 8;
+  return LocateLayout(h, npat, wide_cap).bytes;
 }
 uint64_t locate_workspace_bytes(const cs_fm_index* h, uint64_t npat) {
   return LongBufs::bytes(npat, false) + locate_lo_bytes(h, npat, npat);
@@ -4089,7 +4153,8 @@ cs_status launch_locate_onepass(const cs_fm_index* h, const uint8_t* d_pats, con
   // stream-ordered allocation per call without a workspace, not two)
   const bool lists = long_only || routed || defer;
   const uint64_t lb_bytes = lists ? LongBufs::bytes(npat, long_only) : 0;
-  const uint64_t lo = locate_lo_bytes(h, npat, wide_cap);
+  const LocateLayout L(h, npat, wide_cap);
+  const uint64_t lo = L.bytes;
   const bool use_ws = work.p && work.bytes >= LongBufs::bytes(npat, false) + lo;
   StreamBuf wsb;
   uint8_t* base;
@@ -4103,96 +4168,78 @@ cs_status launch_locate_onepass(const cs_fm_index* h, const uint8_t* d_pats, con
     lo_at = lb_bytes;
   }
   OnePass op;
-  op.rec = reinterpret_cast<uint64_t*>(base + lo_at);
-  op.tiles = op.rec + npat;
-  op.nwide = reinterpret_cast<unsigned long long*>(op.tiles + tiles);
-  op.wide = reinterpret_cast<uint64_t*>(op.nwide + 1);
-  if (h->wide) op.cnt64 = op.wide + 2 * wide_cap;
-  else op.cnt = reinterpret_cast<uint32_t*>(op.wide + 2 * wide_cap);
-  {
-    // after the counts (8-B aligned): on walk-line indexes the tiles' walk counts and slots,
-    // then the chained scan's flags
-    const uint64_t cb = h->wide ? 8 : 4;
-    uint8_t* w = reinterpret_cast<uint8_t*>(op.wide + 2 * wide_cap) + ((npat * cb + 7) & ~7ull);
-    if (kpos != 0) {
-      op.wcnt = reinterpret_cast<uint32_t*>(w);
-      op.walks = reinterpret_cast<uint64_t*>(w + ((tiles * 4 + 7) & ~7ull));
-    }
-    op.sflags = reinterpret_cast<unsigned long long*>(w + locate_walk_bytes(h, npat));
+  uint8_t* const lp = base + lo_at;
+  op.rec = reinterpret_cast<uint64_t*>(lp + L.rec);
+  op.tiles = reinterpret_cast<uint64_t*>(lp + L.tiles);
+  op.nwide = reinterpret_cast<unsigned long long*>(lp + L.nwide);
+  op.wide = reinterpret_cast<uint64_t*>(lp + L.wide);
+  if (h->wide) op.cnt64 = reinterpret_cast<uint64_t*>(lp + L.counts);
+  else op.cnt = reinterpret_cast<uint32_t*>(lp + L.counts);
+  if (kpos != 0) {  // (walk-line indexes)
+    op.wcnt = reinterpret_cast<uint32_t*>(lp + L.wcnt);
+    op.walks = reinterpret_cast<uint64_t*>(lp + L.walks);
   }
+  op.sflags = reinterpret_cast<unsigned long long*>(lp + L.sflags);
   op.sa = static_cast<const uint32_t*>(h->d_sa);
   op.out_offs = d_out_offs;
   op.out_pos = d_out_pos;
   op.cap = d_out_pos ? cap : 0;
   op.wide_cap = wide_cap;
+  op.defer = defer ? 1u : 0u;
   // the search kernel's blocks zero their tiles (and block 0 the wide-range counter); a
   // CS_Q_LONG call, which runs no search kernel, zeroes them here
-  const bool nobar = count_nobar(flags);
   if (long_only) {
     FMX_HIP(hipMemsetAsync(op.tiles, 0, tiles * 8 + 8, st));
     FMX_HIP(hipMemsetAsync(op.sflags, 0, (kScanMaxBlocks + 1) * 8, st));
   }
-  const CountOut co{nullptr, nullptr, nullptr, 0, 8};
-  op.defer = defer ? 1u : 0u;
-  if (gen) {
-    if (h->line_fmt == kFmtQwm && ix.ptab_k && ix.lctx && !ix.wide && qctx_staged(flags))
-      k_count_qctx<U, 8, true><<<(unsigned)tiles, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, 0, limit, op);
-    else
-      FMX_DISPATCH(h, k_locate_one_gen, (unsigned)tiles, ix, d_pats, d_offs, npat, limit, op);
-  } else if (long_only || routed || defer) {
-    LongBufs lb;
+  LongBufs lb;
+  if (lists) {
     cs_status ls = lb.alloc(npat, long_only, st, base, !use_ws);
     if (ls != CS_OK) return ls;
-    if (long_only)
-      ;  // (tiles zeroed above)
-    else if (routed && nobar)
-      k_count_ctx<OccE, U, true, false, 8, true, true, true><<<(unsigned)tiles, kBlk, 0, st>>>(
-          ix, d_pats, d_offs, npat, co, limit, nullptr, 0, op, lb.ll);
-    else if (routed)
-      k_count_ctx<OccE, U, true, false, 8, false, true, true><<<(unsigned)tiles, kBlk, 0, st>>>(
-          ix, d_pats, d_offs, npat, co, limit, nullptr, 0, op, lb.ll);
-    else if (nobar)
-      k_count_ctx<OccE, U, true, false, 8, true, true><<<(unsigned)tiles, kBlk, 0, st>>>(
-          ix, d_pats, d_offs, npat, co, limit, nullptr, 0, op, lb.ll);
-    else
-      k_count_ctx<OccE, U, true, false, 8, false, true><<<(unsigned)tiles, kBlk, 0, st>>>(
-          ix, d_pats, d_offs, npat, co, limit, nullptr, 0, op, lb.ll);
-    FMX_HIP(hipGetLastError());
-    if (long_only || routed) {
-      const unsigned g1 = routed ? long_list_grid(npat, h->list_grid) : grid_for(npat, kBlk, 0xFFFFFFFFu);
-      // CS_QT_LONG_LOADS8 (k_count_long's): 8-B pattern / window loads
-      const bool v0 = (flags & CS_QT_LONG_LOADS8) != 0;
-      if (routed && v0)
-        k_locate_long<0, true><<<g1, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, limit, op, lb.ll);
-      else if (routed)
-        k_locate_long<3, true><<<g1, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, limit, op, lb.ll);
-      else if (v0)
-        k_locate_long<0, false><<<g1, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, limit, op, lb.ll);
-      else
-        k_locate_long<3, false><<<g1, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, limit, op, lb.ll);
-      FMX_HIP(hipGetLastError());
-    }
-    if (!routed)  // (a routed k_locate_long searches what it listed and what was deferred)
-      k_locate_list<<<long_list_grid(npat, h->list_grid), kBlk, 0, st>>>(ix, d_pats, d_offs, npat, limit, op, lb.ll);
-  } else if (kpos == 0 && nobar)
-    k_count_ctx<OccE, U, true, false, 8, true, true><<<(unsigned)tiles, kBlk, 0, st>>>(
-        ix, d_pats, d_offs, npat, co, limit, nullptr, 0, op);
-  else if (kpos == 0)
-    k_count_ctx<OccE, U, true, false, 8, false, true><<<(unsigned)tiles, kBlk, 0, st>>>(
-        ix, d_pats, d_offs, npat, co, limit, nullptr, 0, op);
-  else if (kpos == 1 && nobar)
-    k_count_ctx<OccE, U, true, false, 8, true, true, false, true, 1><<<(unsigned)tiles, kBlk, 0, st>>>(
-        ix, d_pats, d_offs, npat, co, limit, nullptr, 0, op);
-  else if (kpos == 1)
-    k_count_ctx<OccE, U, true, false, 8, false, true, false, true, 1><<<(unsigned)tiles, kBlk, 0, st>>>(
-        ix, d_pats, d_offs, npat, co, limit, nullptr, 0, op);
-  else if (nobar)
-    k_count_ctx<OccE, U, true, false, 8, true, true, false, true, 2><<<(unsigned)tiles, kBlk, 0, st>>>(
-        ix, d_pats, d_offs, npat, co, limit, nullptr, 0, op);
-  else
-    k_count_ctx<OccE, U, true, false, 8, false, true, false, true, 2><<<(unsigned)tiles, kBlk, 0, st>>>(
-        ix, d_pats, d_offs, npat, co, limit, nullptr, 0, op);
+  }
+  const CountOut co{nullptr, nullptr, nullptr, 0, 8};
+  // nobar: the occurrence engine's search without the block barrier, unless CS_QT_BARRIER
+  const bool nobar = count_nobar(flags);
+  // qctx: the quaternary matrix's staged search (as launch_count_ex's), else the generic one
+  const bool qctx = h->line_fmt == kFmtQwm && ix.ptab_k && ix.lctx && !ix.wide && qctx_staged(flags);
+  if (gen && qctx) {
+    k_count_qctx<U, 8, true><<<(unsigned)tiles, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, 0, limit, op);
+  } else if (gen) {
+    with_engine(h->line_fmt, [&](auto engine) {
+      using E = typename decltype(engine)::type;
+      k_locate_one_gen<E><<<(unsigned)tiles, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, limit, op);
+    });
+  } else if (!long_only) {
+    // the staged search; routed, it lists its long patterns (kSkipLong), and only a full-SA
+    // index (kPos 0) routes
+    with_bool(nobar, [&](auto kNoBar) {
+      with_bool(routed, [&](auto kSkipLong) {
+        with_int<0, 1, 2>(kpos, [&](auto kPos) {
+          constexpr bool kLoc = true, kPacked = false, kOne = true, kRng = true;
+          if constexpr (!(kSkipLong && kPos != 0))
+            k_count_ctx<OccE, U, kLoc, kPacked, 8, kNoBar, kOne, kSkipLong, kRng, kPos>
+                <<<(unsigned)tiles, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, limit, /*rec*/ nullptr,
+                                                   /*fixed_m*/ 0, op, lists ? lb.ll : LongList{});
+        });
+      });
+    });
+  }
   FMX_HIP(hipGetLastError());
+  if (long_only || routed) {
+    const unsigned g1 = routed ? long_list_grid(npat, h->list_grid) : grid_for(npat, kBlk, 0xFFFFFFFFu);
+    // v16: 16-B pattern / window loads; CS_QT_LONG_LOADS8 (k_count_long's): 8-B loads
+    const int v16 = (flags & CS_QT_LONG_LOADS8) ? 0 : 3;
+    with_int<3, 0>(v16, [&](auto kV16) {
+      with_bool(routed, [&](auto kList) {
+        k_locate_long<kV16, kList><<<g1, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, limit, op, lb.ll);
+      });
+    });
+    FMX_HIP(hipGetLastError());
+  }
+  if (lists && !routed) {  // (a routed k_locate_long searches what it listed and what was deferred)
+    k_locate_list<<<long_list_grid(npat, h->list_grid), kBlk, 0, st>>>(ix, d_pats, d_offs, npat, limit, op, lb.ll);
+    FMX_HIP(hipGetLastError());
+  }
   // (k_locate_walks: 4 blocks per CU, and one tile per thread)
   const unsigned walk_grid = (unsigned)std::max<uint64_t>(list_blocks_per_device(), (tiles + kBlk - 1) / kBlk);
   // the chained scan (a block per 1024 tiles) while its look-back fits a block, else one block
@@ -4202,18 +4249,12 @@ cs_status launch_locate_onepass(const cs_fm_index* h, const uint8_t* d_pats, con
   else
     k_scan_tiles<<<1, 1024, 0, st>>>(op.tiles, tiles, d_out_offs + npat);
   FMX_HIP(hipGetLastError());
-  if (kpos == 0) {
-    k_locate_emit<U, 0><<<(unsigned)tiles, kBlk, 0, st>>>(ix, npat, op);
-    k_locate_emit_wide<0><<<1024, kBlk, 0, st>>>(ix, op, d_out_offs, d_out_pos);
-  } else if (kpos == 1) {
-    k_locate_emit<U, 1><<<(unsigned)tiles, kBlk, 0, st>>>(ix, npat, op);
-    k_locate_walks<1><<<walk_grid, kBlk, 0, st>>>(ix, op, tiles);
-    k_locate_emit_wide<1><<<1024, kBlk, 0, st>>>(ix, op, d_out_offs, d_out_pos);
-  } else {
-    k_locate_emit<U, 2><<<(unsigned)tiles, kBlk, 0, st>>>(ix, npat, op);
-    k_locate_walks<2><<<walk_grid, kBlk, 0, st>>>(ix, op, tiles);
-    k_locate_emit_wide<2><<<1024, kBlk, 0, st>>>(ix, op, d_out_offs, d_out_pos);
-  }
+  // kPos: positions from the full SA (0), or by the walk over narrow (1) / wide (2) walk lines
+  with_int<0, 1, 2>(kpos, [&](auto kPos) {
+    k_locate_emit<U, kPos><<<(unsigned)tiles, kBlk, 0, st>>>(ix, npat, op);
+    if constexpr (kPos != 0) k_locate_walks<kPos><<<walk_grid, kBlk, 0, st>>>(ix, op, tiles);
+    k_locate_emit_wide<kPos><<<1024, kBlk, 0, st>>>(ix, op, d_out_offs, d_out_pos);
+  });
   FMX_HIP(hipGetLastError());
   FMX_HIP(hipMemcpyAsync(total, d_out_offs + npat, 8, hipMemcpyDeviceToHost, st));
   FMX_HIP(hipStreamSynchronize(st));
@@ -4228,28 +4269,38 @@ cs_status launch_locate_ranges(const cs_fm_index* h, const uint8_t* d_pats,
   FMX_HIP(cnt.alloc((npat + 1) * 8, st));
   flags = call_flags(h, flags);
   const DevIndex ix = query_dev(h, flags);
-  if ((h->line_fmt == kFmtOcc || h->line_fmt == kFmtLOcc) && ix.lctx && ix.ptab_k) {
-    // patterns per lane: CS_QT_LOCATE_U1 (CS_FM_LOCATE_U=1) one, else two
-    const int U = (flags & CS_QT_LOCATE_U1) ? 1 : 2;
+  // staged: k_count_ctx's locate form, occurrence lines (learned or not) with a prefix table
+  // and left contexts; else the general search on any engine
+  const bool staged = (h->line_fmt == kFmtOcc || h->line_fmt == kFmtLOcc) && ix.lctx && ix.ptab_k;
+  const bool learned = h->line_fmt == kFmtLOcc;
+  // U, patterns per lane: 2; CS_QT_LOCATE_U1 (CS_FM_LOCATE_U=1) one, which learned lines ignore
+  const int U = !learned && (flags & CS_QT_LOCATE_U1) ? 1 : 2;
+  // nobar: unless CS_QT_BARRIER, for two patterns per lane over occurrence lines; the U = 1
+  // form and learned lines keep the barrier whatever the flag says
+  const bool nobar = !learned && U == 2 && count_nobar(flags);
+  if (staged) {
     const CountOut co{cnt.p, nullptr, nullptr, 0, 8};
-    const unsigned g2 = grid_for((npat + 1) / 2, kBlk, 0xFFFFFFFFu);
-    if (h->line_fmt == kFmtOcc && U == 1)
-      k_count_ctx<OccE, 1, true, false, 8><<<grid_for(npat, kBlk, 0xFFFFFFFFu), kBlk, 0, st>>>(
-          ix, d_pats, d_offs, npat, co, limit, d_sp, 0);
-    else if (h->line_fmt == kFmtOcc && count_nobar(flags))
-      k_count_ctx<OccE, 2, true, false, 8, true><<<g2, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co,
-                                                                      limit, d_sp, 0);
-    else if (h->line_fmt == kFmtOcc)  // staged, two patterns per lane
-      k_count_ctx<OccE, 2, true, false, 8><<<g2, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, limit,
-                                                                 d_sp, 0);
-    else
-      k_count_ctx<LOccE, 2, true, false, 8><<<g2, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, co, limit,
-                                                                  d_sp, 0);
-    FMX_HIP(hipGetLastError());
+    const unsigned g = grid_for((npat + U - 1) / U, kBlk, 0xFFFFFFFFu);
+    with_bool(learned, [&](auto kLearned) {
+      with_int<2, 1>(U, [&](auto kU) {
+        with_bool(nobar, [&](auto kNoBar) {
+          using E = std::conditional_t<kLearned, LOccE, OccE>;
+          constexpr bool kLoc = true, kPacked = false;
+          // the forms the choices above can make
+          if constexpr (kLearned ? kU == 2 && !kNoBar : kU == 2 || !kNoBar)
+            k_count_ctx<E, kU, kLoc, kPacked, 8, kNoBar><<<g, kBlk, 0, st>>>(
+                ix, d_pats, d_offs, npat, co, limit, /*rec*/ d_sp, /*fixed_m*/ 0);
+        });
+      });
+    });
   } else {
-    FMX_DISPATCH(h, k_locate_ranges, grid_for(npat + 1, kBlk, 0xFFFFFFFFu), ix, d_pats,
-                 d_offs, npat, limit, d_sp, cnt.as<uint64_t>());
+    with_engine(h->line_fmt, [&](auto engine) {
+      using E = typename decltype(engine)::type;
+      k_locate_ranges<E><<<grid_for(npat + 1, kBlk, 0xFFFFFFFFu), kBlk, 0, st>>>(
+          ix, d_pats, d_offs, npat, limit, d_sp, cnt.as<uint64_t>());
+    });
   }
+  FMX_HIP(hipGetLastError());
   size_t tb = 0;
   FMX_HIP(rocprim::exclusive_scan(nullptr, tb, cnt.as<uint64_t>(), d_out_offs, (uint64_t)0,
                                   npat + 1, rocprim::plus<uint64_t>(), st));
@@ -4260,53 +4311,6 @@ cs_status launch_locate_ranges(const cs_fm_index* h, const uint8_t* d_pats,
   FMX_HIP(hipStreamSynchronize(st));
   return CS_OK;
 }
-
-// Phase 2 with the full suffix array, fused (no rows buffer): each pattern's rows come
-// from its record (as k_expand_rows) and go straight through SA: SA[row] - k (mod n) for
-// a window row k characters before the end, SA[row] otherwise.  A lane
-// takes a pattern of at most kLocSmall rows (every context window: <= kLocSpanBits);
-// wider plain ranges are listed for k_locate_sa_wide, a block per range.
-__global__ __launch_bounds__(kBlk) void k_locate_sa(const uint32_t* __restrict__ sa, uint64_t n,
-                                                    const uint64_t* __restrict__ sp,
-                                                    const uint64_t* __restrict__ offs, uint64_t npat,
-                                                    uint64_t* __restrict__ out,
-                                                    uint64_t* __restrict__ wide,
-                                                    unsigned long long* __restrict__ nwide) {
-  const uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t q = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; q < npat; q += gs) {
-    const uint64_t a = offs[q], c = offs[q + 1] - a, s = sp[q];
-    if (!c) continue;
-    if (s & kLocCtx) {
-      uint64_t r0, adj;
-      uint32_t rel;
-      loc_window(s, r0, adj, rel);
-      for (uint64_t j = 0; j < c; ++j) {
-        const uint32_t f = (uint32_t)__ffs(rel) - 1u;
-        const uint64_t p = load_sa(sa, r0 + f);
-        st_out(out + a + j, p >= adj ? p - adj : p + n - adj);
-        rel &= rel - 1u;
-      }
-    } else if (c <= kLocSmall) {
-      for (uint64_t j = 0; j < c; ++j) st_out(out + a + j, (uint64_t)sa[s + j]);
-    } else {
-      wide[atomicAdd(nwide, 1ull)] = q;
-    }
-  }
-}
-
-__global__ __launch_bounds__(kBlk) void k_locate_sa_wide(const uint32_t* __restrict__ sa,
-                                                         const uint64_t* __restrict__ sp,
-                                                         const uint64_t* __restrict__ offs,
-                                                         uint64_t* __restrict__ out,
-                                                         const uint64_t* __restrict__ wide,
-                                                         const unsigned long long* __restrict__ nwide) {
-  const uint64_t nw = *nwide;
-  for (uint64_t e = blockIdx.x; e < nw; e += gridDim.x) {
-    const uint64_t q = wide[e], a = offs[q], c = offs[q + 1] - a, s = sp[q];
-    for (uint64_t j = threadIdx.x; j < c; j += blockDim.x) st_out(out + a + j, (uint64_t)sa[s + j]);
-  }
-}
-
 
 cs_status launch_locate_walk(const cs_fm_index* h, const uint64_t* d_sp,
                              const uint64_t* d_out_offs, uint64_t npat, uint64_t total,
@@ -4342,33 +4346,30 @@ cs_status launch_locate_walk(const cs_fm_index* h, const uint64_t* d_sp,
   const DevIndex ix = query_dev(h, flags);
   unsigned long long* err =
       err_word ? err_word : reinterpret_cast<unsigned long long*>(h->d_err);
+  // short_walk: walk lines with text-position marks, a short walk per position; unless
+  // CS_QT_WALK_PERSISTENT (CS_FM_WALK_PERSISTENT=1): the persistent walk over a rows buffer
+  const bool short_walk = ix.walk && h->walk_marks == 2 && !(flags & CS_QT_WALK_PERSISTENT);
+  // fused: the short walks straight from the records (no rows buffer); unless CS_QT_WALK_ROWS
+  // (CS_FM_WALK_ROWS=1): from an expanded rows buffer (k_expand_rows + k_walk_short)
+  const bool fused = short_walk && !(flags & CS_QT_WALK_ROWS);
+  // qwm: the walk lines are a quaternary matrix's (kQ); pow2: the sample stride is a power
+  // of two (POW2; the persistent walk over the engine, an index without walk lines)
+  const bool qwm = h->line_fmt == kFmtQwm;
   const bool pow2 = ix.stride_shift != 0xFFFFFFFFu;
-  // CS_QT_WALK_PERSISTENT (CS_FM_WALK_PERSISTENT=1): the persistent walk over a rows buffer;
-  // CS_QT_WALK_ROWS (CS_FM_WALK_ROWS=1): short walks from an expanded rows buffer
-  // (k_expand_rows + k_walk_short) instead of straight from the records
-  const bool persistent = (flags & CS_QT_WALK_PERSISTENT) != 0;
-  if (ix.walk && h->walk_marks == 2 && !persistent && !(flags & CS_QT_WALK_ROWS)) {
-    // short walks straight from the records (no rows buffer)
+  if (fused) {
     StreamBuf wide;
     FMX_HIP(wide.alloc((total / (kLocSmall + 1) + 1) * 8 + 8, st));
     unsigned long long* nwide = wide.as<unsigned long long>();
     FMX_HIP(hipMemsetAsync(nwide, 0, 8, st));
     uint64_t* wl = wide.as<uint64_t>() + 1;
-    const bool q = h->line_fmt == kFmtQwm;
     const unsigned g = grid_for(npat, kBlk, 0xFFFFFFFFu);
-    if (h->wide && q) {
-      k_walk_fused<WalkLineW, true><<<g, kBlk, 0, st>>>(ix, d_sp, d_out_offs, npat, d_out_pos, wl, nwide, err, steps_only);
-      k_walk_fused_wide<WalkLineW, true><<<1024, kBlk, 0, st>>>(ix, d_sp, d_out_offs, d_out_pos, wl, nwide, err, steps_only);
-    } else if (h->wide) {
-      k_walk_fused<WalkLineW, false><<<g, kBlk, 0, st>>>(ix, d_sp, d_out_offs, npat, d_out_pos, wl, nwide, err, steps_only);
-      k_walk_fused_wide<WalkLineW, false><<<1024, kBlk, 0, st>>>(ix, d_sp, d_out_offs, d_out_pos, wl, nwide, err, steps_only);
-    } else if (q) {
-      k_walk_fused<WalkLine, true><<<g, kBlk, 0, st>>>(ix, d_sp, d_out_offs, npat, d_out_pos, wl, nwide, err, steps_only);
-      k_walk_fused_wide<WalkLine, true><<<1024, kBlk, 0, st>>>(ix, d_sp, d_out_offs, d_out_pos, wl, nwide, err, steps_only);
-    } else {
-      k_walk_fused<WalkLine, false><<<g, kBlk, 0, st>>>(ix, d_sp, d_out_offs, npat, d_out_pos, wl, nwide, err, steps_only);
-      k_walk_fused_wide<WalkLine, false><<<1024, kBlk, 0, st>>>(ix, d_sp, d_out_offs, d_out_pos, wl, nwide, err, steps_only);
-    }
+    with_walk_line(h->wide, [&](auto line) {
+      with_bool(qwm, [&](auto kQ) {
+        using W = typename decltype(line)::type;
+        k_walk_fused<W, kQ><<<g, kBlk, 0, st>>>(ix, d_sp, d_out_offs, npat, d_out_pos, wl, nwide, err, steps_only);
+        k_walk_fused_wide<W, kQ><<<1024, kBlk, 0, st>>>(ix, d_sp, d_out_offs, d_out_pos, wl, nwide, err, steps_only);
+      });
+    });
     FMX_HIP(hipGetLastError());
     return CS_OK;
   }
@@ -4378,45 +4379,23 @@ cs_status launch_locate_walk(const cs_fm_index* h, const uint64_t* d_sp,
                                                               rows.as<uint64_t>());
   FMX_HIP(hipGetLastError());
   const uint64_t* r = rows.as<uint64_t>();
-  if (ix.walk && h->walk_marks == 2 && !persistent) {
-    const bool q = h->line_fmt == kFmtQwm;
-    const unsigned g = grid_for(total, kBlk, 0xFFFFFFFFu);
-    if (h->wide && q)
-      k_walk_short<WalkLineW, true><<<g, kBlk, 0, st>>>(ix, r, total, d_out_pos, err, steps_only);
-    else if (h->wide)
-      k_walk_short<WalkLineW, false><<<g, kBlk, 0, st>>>(ix, r, total, d_out_pos, err, steps_only);
-    else if (q)
-      k_walk_short<WalkLine, true><<<g, kBlk, 0, st>>>(ix, r, total, d_out_pos, err, steps_only);
-    else
-      k_walk_short<WalkLine, false><<<g, kBlk, 0, st>>>(ix, r, total, d_out_pos, err, steps_only);
-  } else if (ix.walk) {
-    const bool q = h->line_fmt == kFmtQwm;
-    if (h->wide && q)
-      k_walk_lines<WalkLineW, true><<<blocks, kBlk, 0, st>>>(ix, r, total, chunk, d_out_pos, err, steps_only);
-    else if (h->wide)
-      k_walk_lines<WalkLineW, false><<<blocks, kBlk, 0, st>>>(ix, r, total, chunk, d_out_pos, err, steps_only);
-    else if (q)
-      k_walk_lines<WalkLine, true><<<blocks, kBlk, 0, st>>>(ix, r, total, chunk, d_out_pos, err, steps_only);
-    else
-      k_walk_lines<WalkLine, false><<<blocks, kBlk, 0, st>>>(ix, r, total, chunk, d_out_pos, err, steps_only);
-  } else if (h->line_fmt == kFmtQwm) {
-    if (pow2) k_walk<QWM, true><<<blocks, kBlk, 0, st>>>(ix, r, total, chunk, d_out_pos, err, steps_only);
-    else k_walk<QWM, false><<<blocks, kBlk, 0, st>>>(ix, r, total, chunk, d_out_pos, err, steps_only);
-  } else if (h->line_fmt == kFmtOcc) {
-    if (pow2) k_walk<OccE, true><<<blocks, kBlk, 0, st>>>(ix, r, total, chunk, d_out_pos, err, steps_only);
-    else k_walk<OccE, false><<<blocks, kBlk, 0, st>>>(ix, r, total, chunk, d_out_pos, err, steps_only);
-  } else if (h->line_fmt == kFmtLOcc) {
-    if (pow2) k_walk<LOccE, true><<<blocks, kBlk, 0, st>>>(ix, r, total, chunk, d_out_pos, err, steps_only);
-    else k_walk<LOccE, false><<<blocks, kBlk, 0, st>>>(ix, r, total, chunk, d_out_pos, err, steps_only);
-  } else if (h->line_fmt == kFmtLine32) {
-    if (pow2) k_walk<WM<Line32>, true><<<blocks, kBlk, 0, st>>>(ix, r, total, chunk, d_out_pos, err, steps_only);
-    else k_walk<WM<Line32>, false><<<blocks, kBlk, 0, st>>>(ix, r, total, chunk, d_out_pos, err, steps_only);
-  } else if (h->line_fmt == kFmtLine32W) {
-    if (pow2) k_walk<WM<Line32W>, true><<<blocks, kBlk, 0, st>>>(ix, r, total, chunk, d_out_pos, err, steps_only);
-    else k_walk<WM<Line32W>, false><<<blocks, kBlk, 0, st>>>(ix, r, total, chunk, d_out_pos, err, steps_only);
-  } else {
-    if (pow2) k_walk<WM<Line64>, true><<<blocks, kBlk, 0, st>>>(ix, r, total, chunk, d_out_pos, err, steps_only);
-    else k_walk<WM<Line64>, false><<<blocks, kBlk, 0, st>>>(ix, r, total, chunk, d_out_pos, err, steps_only);
+  if (ix.walk) {  // over walk lines: the short walks, or the persistent walk
+    with_walk_line(h->wide, [&](auto line) {
+      with_bool(qwm, [&](auto kQ) {
+        using W = typename decltype(line)::type;
+        if (short_walk)
+          k_walk_short<W, kQ><<<grid_for(total, kBlk, 0xFFFFFFFFu), kBlk, 0, st>>>(ix, r, total, d_out_pos, err, steps_only);
+        else
+          k_walk_lines<W, kQ><<<blocks, kBlk, 0, st>>>(ix, r, total, chunk, d_out_pos, err, steps_only);
+      });
+    });
+  } else {  // the persistent walk over the engine's own LF
+    with_engine(h->line_fmt, [&](auto engine) {
+      with_bool(pow2, [&](auto POW2) {
+        using E = typename decltype(engine)::type;
+        k_walk<E, POW2><<<blocks, kBlk, 0, st>>>(ix, r, total, chunk, d_out_pos, err, steps_only);
+      });
+    });
   }
   FMX_HIP(hipGetLastError());
   return CS_OK;  // rows are freed in stream order after the walk
@@ -4456,13 +4435,12 @@ cs_status launch_level_rank1(const cs_fm_index* h, int level, const uint64_t* d_
     return CS_ERR_UNSUPPORTED;
   }
   if (!k) return CS_OK;
-  const unsigned g = grid_for(k, kBlk, 0xFFFFFFFFu);
-  if (h->line_fmt == kFmtLine32)
-    k_level_rank1<Line32><<<g, kBlk, 0, st>>>(h->dev(), level, d_pos, k, d_out);
-  else if (h->line_fmt == kFmtLine32W)
-    k_level_rank1<Line32W><<<g, kBlk, 0, st>>>(h->dev(), level, d_pos, k, d_out);
-  else
-    k_level_rank1<Line64><<<g, kBlk, 0, st>>>(h->dev(), level, d_pos, k, d_out);
+  // the engine's rank lines F: one of the binary wavelet matrix's (the others left above)
+  with_engine(h->line_fmt, [&](auto engine) {
+    using F = typename wm_line<typename decltype(engine)::type>::type;
+    if constexpr (!std::is_void_v<F>)
+      k_level_rank1<F><<<grid_for(k, kBlk, 0xFFFFFFFFu), kBlk, 0, st>>>(h->dev(), level, d_pos, k, d_out);
+  });
   FMX_HIP(hipGetLastError());
   return CS_OK;
 }
@@ -4470,24 +4448,34 @@ cs_status launch_level_rank1(const cs_fm_index* h, int level, const uint64_t* d_
 cs_status launch_wt_rank(const cs_fm_index* h, const uint8_t* d_syms, const uint64_t* d_pos,
                          uint64_t k, uint64_t* d_out, hipStream_t st) {
   if (!k) return CS_OK;
-  FMX_DISPATCH(h, k_wt_rank, grid_for(k, kBlk, 0xFFFFFFFFu), h->dev(), d_syms, d_pos, k, d_out);
+  with_engine(h->line_fmt, [&](auto engine) {
+    using E = typename decltype(engine)::type;
+    k_wt_rank<E><<<grid_for(k, kBlk, 0xFFFFFFFFu), kBlk, 0, st>>>(h->dev(), d_syms, d_pos, k, d_out);
+  });
+  FMX_HIP(hipGetLastError());
+  return CS_OK;
+}
+
+// LF of the rows in d_rows: the mapped rows to d_out, the BWT symbols to d_sym (either null)
+static cs_status launch_k_lf(const cs_fm_index* h, const uint64_t* d_rows, uint64_t k, uint64_t* d_out,
+                             uint8_t* d_sym, hipStream_t st) {
+  if (!k) return CS_OK;
+  with_engine(h->line_fmt, [&](auto engine) {
+    using E = typename decltype(engine)::type;
+    k_lf<E><<<grid_for(k, kBlk, 0xFFFFFFFFu), kBlk, 0, st>>>(h->dev(), d_rows, k, d_out, d_sym);
+  });
+  FMX_HIP(hipGetLastError());
   return CS_OK;
 }
 
 cs_status launch_wt_access(const cs_fm_index* h, const uint64_t* d_pos, uint64_t k,
                            uint8_t* d_out, hipStream_t st) {
-  if (!k) return CS_OK;
-  FMX_DISPATCH(h, k_lf, grid_for(k, kBlk, 0xFFFFFFFFu), h->dev(), d_pos, k, (uint64_t*)nullptr,
-               d_out);
-  return CS_OK;
+  return launch_k_lf(h, d_pos, k, nullptr, d_out, st);
 }
 
 cs_status launch_lf(const cs_fm_index* h, const uint64_t* d_rows, uint64_t k, uint64_t* d_out,
                     hipStream_t st) {
-  if (!k) return CS_OK;
-  FMX_DISPATCH(h, k_lf, grid_for(k, kBlk, 0xFFFFFFFFu), h->dev(), d_rows, k, d_out,
-               (uint8_t*)nullptr);
-  return CS_OK;
+  return launch_k_lf(h, d_rows, k, d_out, nullptr, st);
 }
 
 }  // namespace fmx

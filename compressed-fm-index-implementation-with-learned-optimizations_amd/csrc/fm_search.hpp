@@ -1,9 +1,9 @@
 // fm_search.hpp — device-side search helpers shared by the query kernels (fm_query.hip)
 // and the index-structure builders (fm_structs.hip): the node table in LDS, one
 // backward-search step per rank engine, the prefix-table / left-context / record
-// lookups and the search loops the kernels are built from, plus the engine dispatch
-// macros.  Everything sits in an anonymous namespace: each translation unit
-// instantiates the templates it launches.
+// lookups and the search loops the kernels are built from, plus the dispatch helpers
+// (with_engine, with_walk_line, with_bool, with_int).  Everything sits in an anonymous
+// namespace: each translation unit instantiates the templates it launches.
 #pragma once
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -961,58 +961,56 @@ __device__ __forceinline__ uint64_t locate_search(const DevIndex& ix, const Node
 
 }  // namespace
 
-// Dispatch on the handle's engine / rank-line format.
-#define FMX_DISPATCH(h, KERNEL, GRID, ...)                                      \
-  do {                                                                          \
-    if ((h)->line_fmt == kFmtOcc)                                               \
-      KERNEL<OccE><<<(GRID), kBlk, 0, st>>>(__VA_ARGS__);                       \
-    else if ((h)->line_fmt == kFmtLOcc)                                         \
-      KERNEL<LOccE><<<(GRID), kBlk, 0, st>>>(__VA_ARGS__);                      \
-    else if ((h)->line_fmt == kFmtQwm)                                          \
-      KERNEL<QWM><<<(GRID), kBlk, 0, st>>>(__VA_ARGS__);                        \
-    else if ((h)->line_fmt == kFmtLine32)                                       \
-      KERNEL<WM<Line32>><<<(GRID), kBlk, 0, st>>>(__VA_ARGS__);                 \
-    else if ((h)->line_fmt == kFmtLine32W)                                      \
-      KERNEL<WM<Line32W>><<<(GRID), kBlk, 0, st>>>(__VA_ARGS__);                \
-    else                                                                        \
-      KERNEL<WM<Line64>><<<(GRID), kBlk, 0, st>>>(__VA_ARGS__);                 \
-    FMX_HIP(hipGetLastError());                                                 \
-  } while (0)
+// ---- dispatch: a runtime value as a compile-time tag, handed to a generic lambda ----
+// Host code states a kernel's template arguments through these.  Each helper picks the tag of
+// its runtime value and calls f(tag); the lambda's parameter is named after the template
+// parameter it fills.  A bool / int tag converts to its constant (k<..., kNoBar, ...>); a type
+// tag carries its type (typename decltype(engine)::type).  Plain branches the compiler
+// inlines: nothing allocates, nothing is called indirectly.  A lambda names only the
+// combinations that exist (if constexpr), so no helper instantiates a kernel of its own.
+template <class T>
+struct TypeTag {
+  using type = T;
+};
+template <bool B>
+using BoolTag = std::integral_constant<bool, B>;
+template <int I>
+using IntTag = std::integral_constant<int, I>;
 
-// Same, with a second template argument after the engine.
-#define FMX_DISPATCH2(h, KERNEL, TARG, GRID, ...)                               \
-  do {                                                                          \
-    if ((h)->line_fmt == kFmtOcc)                                               \
-      KERNEL<OccE, TARG><<<(GRID), kBlk, 0, st>>>(__VA_ARGS__);                 \
-    else if ((h)->line_fmt == kFmtLOcc)                                         \
-      KERNEL<LOccE, TARG><<<(GRID), kBlk, 0, st>>>(__VA_ARGS__);                \
-    else if ((h)->line_fmt == kFmtQwm)                                          \
-      KERNEL<QWM, TARG><<<(GRID), kBlk, 0, st>>>(__VA_ARGS__);                  \
-    else if ((h)->line_fmt == kFmtLine32)                                       \
-      KERNEL<WM<Line32>, TARG><<<(GRID), kBlk, 0, st>>>(__VA_ARGS__);           \
-    else if ((h)->line_fmt == kFmtLine32W)                                      \
-      KERNEL<WM<Line32W>, TARG><<<(GRID), kBlk, 0, st>>>(__VA_ARGS__);          \
-    else                                                                        \
-      KERNEL<WM<Line64>, TARG><<<(GRID), kBlk, 0, st>>>(__VA_ARGS__);           \
-    FMX_HIP(hipGetLastError());                                                 \
-  } while (0)
-
-// Same, one 64-lane block.
-#define FMX_DISPATCH1(h, KERNEL, ...)                                           \
-  do {                                                                          \
-    if ((h)->line_fmt == kFmtOcc)                                               \
-      KERNEL<OccE><<<1, 64, 0, st>>>(__VA_ARGS__);                              \
-    else if ((h)->line_fmt == kFmtLOcc)                                         \
-      KERNEL<LOccE><<<1, 64, 0, st>>>(__VA_ARGS__);                             \
-    else if ((h)->line_fmt == kFmtQwm)                                          \
-      KERNEL<QWM><<<1, 64, 0, st>>>(__VA_ARGS__);                               \
-    else if ((h)->line_fmt == kFmtLine32)                                       \
-      KERNEL<WM<Line32>><<<1, 64, 0, st>>>(__VA_ARGS__);                        \
-    else if ((h)->line_fmt == kFmtLine32W)                                      \
-      KERNEL<WM<Line32W>><<<1, 64, 0, st>>>(__VA_ARGS__);                       \
-    else                                                                        \
-      KERNEL<WM<Line64>><<<1, 64, 0, st>>>(__VA_ARGS__);                        \
-    FMX_HIP(hipGetLastError());                                                 \
-  } while (0)
+// the engine of the handle's rank-line format (cs_fm_index::line_fmt)
+template <class F>
+decltype(auto) with_engine(uint32_t line_fmt, F&& f) {
+  if (line_fmt == kFmtOcc) return f(TypeTag<OccE>{});
+  if (line_fmt == kFmtLOcc) return f(TypeTag<LOccE>{});
+  if (line_fmt == kFmtQwm) return f(TypeTag<QWM>{});
+  if (line_fmt == kFmtLine32) return f(TypeTag<WM<Line32>>{});
+  if (line_fmt == kFmtLine32W) return f(TypeTag<WM<Line32W>>{});
+  return f(TypeTag<WM<Line64>>{});
+}
+// the rank lines F of a binary wavelet matrix engine WM<F>; void for the other engines
+template <class E>
+struct wm_line {
+  using type = void;
+};
+template <class F>
+struct wm_line<WM<F>> {
+  using type = F;
+};
+// the walk lines of a narrow / wide index (fm_device.hpp WalkLine, WalkLineW)
+template <class F>
+decltype(auto) with_walk_line(bool wide, F&& f) {
+  return wide ? f(TypeTag<WalkLineW>{}) : f(TypeTag<WalkLine>{});
+}
+template <class F>
+decltype(auto) with_bool(bool b, F&& f) {
+  return b ? f(BoolTag<true>{}) : f(BoolTag<false>{});
+}
+// v among the closed set I0, Is... (the last one stands for any other value): the count
+// width <8, 4, 1>, kPos and kWalk <0, 1, 2>, kV16 <3, 0>, patterns per lane <2, 1, 4>
+template <int I0, int... Is, class F>
+decltype(auto) with_int(int v, F&& f) {
+  if constexpr (sizeof...(Is) == 0) return f(IntTag<I0>{});
+  else return v == I0 ? f(IntTag<I0>{}) : with_int<Is...>(v, f);
+}
 
 }  // namespace fmx

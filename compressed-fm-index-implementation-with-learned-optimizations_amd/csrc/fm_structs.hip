@@ -132,7 +132,11 @@ cs_status build_prefix_table(cs_fm_index* h, hipStream_t st) {
   ix.ptab = nullptr;  // the builder itself searches from C[]
   uint64_t wmax = kPtabEsc;
   if (const char* e = build_opt("CS_FM_PTAB_WMAX")) wmax = std::strtoull(e, nullptr, 10);
-  FMX_DISPATCH(h, k_build_ptab, grid_for(entries, kBlk, 65536), ix, entries, h->d_ptab, wmax);
+  with_engine(h->line_fmt, [&](auto engine) {
+    using E = typename decltype(engine)::type;
+    k_build_ptab<E><<<grid_for(entries, kBlk, 65536), kBlk, 0, st>>>(ix, entries, h->d_ptab, wmax);
+  });
+  FMX_HIP(hipGetLastError());
   FMX_HIP(hipStreamSynchronize(st));
   return CS_OK;
 }

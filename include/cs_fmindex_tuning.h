@@ -73,7 +73,8 @@ extern "C" {
  * PASS_MAX=<bytes>, the handle defaults of the selectors above (LONG_ROUTE=0, COUNT_U=4 ...),
  * GENERAL_LIST_MIN, LIST_GRID, HOST_CHUNK.  With an options string (empty included) the build
  * reads no environment variable: a name not given takes its default.  options == NULL is
- * cs_fm_build_from_text / cs_fm_build_from_device_text (text_on_device != 0), which read the
+ * cs_fm_build_from_text / cs_fm_build_from_device_text (text_on_device != 0): the build uses
+ * the calling thread's cs_fm_set_build_options options if any are set, otherwise the
  * environment.  A malformed pair or an unknown name fails with CS_ERR_INVALID
  * (cs_fm_last_error names it).  Results never depend on the options, only footprint and
  * throughput do. */

@@ -346,7 +346,7 @@ def test_count_every_text_vs_oracle(built, name):
 
 @pytest.mark.parametrize("name", sorted(TEXTS))
 def test_count_fixed_length(built, name):
-    """cs_fm_count_fixed_device — patterns of one length m back to back, no offsets
+    """cs_fm_count_device with d_offs = NULL — patterns of one length m back to back, no offsets
     array — equals the oracle's count for substrings and mutants, and n for m = 0."""
     g, o = built(name)
     t = TEXTS[name]
@@ -729,7 +729,7 @@ def _count_bo(g, buf, offs, flags=0):
 
 
 def _count_ex(g, pats, width=8, flags=0, exc_cap=1 << 16):
-    """count through cs_fm_count_batch_device_ex -> (counts as uint64, exception pairs)."""
+    """count through cs_fm_count_device under `flags` -> (counts as uint64, exception pairs)."""
     buf, offs = O.pack_patterns(pats)
     d_buf = torch.from_numpy(buf.copy()).cuda()
     d_offs = torch.from_numpy(offs.astype(np.int64)).cuda()
@@ -833,7 +833,7 @@ def test_count_verify_long(built, pkg, name):
     if lp:
         assert g.count_batch([pats[i] for i in lp]).tolist() == [want[i] for i in lp], name
         assert g.count_batch([pats[i] for i in lp] + [b"A"]).tolist()[:-1] == [want[i] for i in lp], name
-    # fixed-length batches (cs_fm_count_fixed_device, no offsets array): 33 and 64 through
+    # fixed-length batches (cs_fm_count_device with fixed_m, no offsets array): 33 and 64 through
     # the staged kernel's general search, 130 through the long-pattern kernel (m > 96)
     for m in (33, 64, 130):
         if n < m:
@@ -867,7 +867,7 @@ def _locate_two_phase(g, pats, lim, flags):
 
 
 def _locate_one(g, pats, lim, flags=0):
-    """cs_fm_locate_device_ex: per pattern its positions (a first call for the total)."""
+    """cs_fm_locate_device under `flags`: per pattern its positions (a first call for the total)."""
     buf, offs = O.pack_patterns(pats)
     d_buf = torch.from_numpy(buf.copy()).cuda()
     d_offs = torch.from_numpy(offs.astype(np.int64)).cuda()
@@ -1016,7 +1016,7 @@ def test_locate_one_call(built, pkg, name):
         pos = d_pos[:tot].cpu().numpy()
         for q, p in enumerate(pats):
             assert pos[oo[q]:oo[q + 1]].tolist() == want[q], (name, lim, p)
-        if lim == 40:  # cs_fm_locate_device_ex under CS_Q_NO_PREFIX | CS_Q_NO_CONTEXTS: the two phases
+        if lim == 40:  # cs_fm_locate_device under CS_Q_NO_PREFIX | CS_Q_NO_CONTEXTS: the two phases
             assert _locate_one(g, pats, lim, 3) == want, (name, lim)
         if tot:
             d_oo2 = torch.zeros(npat + 1, dtype=torch.int64, device="cuda")
@@ -1165,12 +1165,15 @@ def test_repetitive_text_vs_oracle(pkg):
 
 def test_selectors_without_a_variant(pkg):
     """The tuning selectors that no engine variant turns on give the oracle's answers:
-    CS_QT_COUNT_U4 (four patterns per lane in the staged count) and CS_QT_BARRIER (its general
-    search behind a block barrier) on a uniform and a repetitive text; CS_QT_WALK_PERSISTENT
-    (phase 2's persistent walk kernel) and CS_QT_WALK_ROWS (walks from an expanded rows buffer),
-    the two phases forced with CS_QT_NO_ONEPASS, on an index without the full suffix array, at
-    limits that cut ranges and at ones that do not; and position samples at the SSA's stride
-    (build option PSTRIDE=32: locate walks and extract by LF inversion)."""
+    CS_QT_COUNT_U1 / CS_QT_COUNT_U4 (one / four patterns per lane in the staged count) and
+    CS_QT_BARRIER (its general search behind a block barrier) on a uniform and a repetitive text;
+    CS_QT_WALK_PERSISTENT (phase 2's persistent walk kernel), CS_QT_WALK_ROWS (walks from an
+    expanded rows buffer) and CS_QT_LOCATE_U1 (phase 1 with one pattern per lane), the two phases
+    forced with CS_QT_NO_ONEPASS, on an index without the full suffix array, at limits that cut
+    ranges and at ones that do not; CS_QT_ONEPASS_SA (the one-call locate over the full suffix
+    array only) on that index, where the call falls back to the two phases, and on a default
+    build, where it runs from the suffix array; and position samples at the SSA's stride (build
+    option PSTRIDE=32: locate walks and extract by LF inversion)."""
     rng = np.random.default_rng(31)
     seed = rng.choice(list(b"ACGT"), 2000).astype(np.uint8)
     rep = np.tile(seed, 100)
@@ -1188,17 +1191,22 @@ def test_selectors_without_a_variant(pkg):
         pats += [b"", b"N" * 5, t[:25], t[-26:-1]]
         buf, offs = O.pack_patterns(pats)
         want = o.count_batch(buf=buf, offs=offs, nthreads=8)
+        assert np.array_equal(_count_bo(g, buf, offs, flags=pkg.QT_COUNT_U1), want), name
         assert np.array_equal(_count_bo(g, buf, offs, flags=pkg.QT_COUNT_U4), want), name
         assert np.array_equal(_count_bo(g, buf, offs, flags=pkg.QT_BARRIER), want), name
         sub = pats[::5]
         b2, o2 = O.pack_patterns(sub)
         for lim in (3, 100_000):
             woffs, wpos = o.locate_batch(buf=b2, offs=o2, limit=lim, nthreads=8)
-            for sel in (pkg.QT_WALK_PERSISTENT, pkg.QT_WALK_ROWS):
-                got = _locate_one(g, sub, lim, flags=pkg.QT_NO_ONEPASS | sel)
-                assert np.array_equal(np.cumsum([0] + [len(q) for q in got]), woffs.astype(np.int64)), (name, lim)
+            sels = [pkg.QT_NO_ONEPASS | s for s in (pkg.QT_WALK_PERSISTENT, pkg.QT_WALK_ROWS, pkg.QT_LOCATE_U1)]
+            runs = [(g, f) for f in sels]
+            if name == "dna" and lim == 3:  # without the full SA (the two phases) and with it
+                runs += [(g, pkg.QT_ONEPASS_SA), (pkg.FMIndex.build_from_text(t), pkg.QT_ONEPASS_SA)]
+            for gi, f in runs:
+                got = _locate_one(gi, sub, lim, flags=f)
+                assert np.array_equal(np.cumsum([0] + [len(q) for q in got]), woffs.astype(np.int64)), (name, lim, f)
                 flat = [x for q in got for x in q]
-                assert np.array_equal(np.asarray(flat, np.int64), wpos.astype(np.int64)), (name, lim)
+                assert np.array_equal(np.asarray(flat, np.int64), wpos.astype(np.int64)), (name, lim, f)
     t = texts["dna"]
     with _env(CS_FM_PSTRIDE="32", CS_FM_FULL_SA="0", CS_FM_DEVICE_TEXT="0"):
         g = pkg.FMIndex.build_from_text(t)

@@ -1,5 +1,5 @@
-"""The caller's workspace (cs_fm_workspace_bytes, cs_fm_count_device_ws, cs_fm_locate_device_ws;
-include/cs_fmindex.h) — the path the headline count and the one-call locate bench legs run.
+"""The caller's workspace (cs_fm_workspace_bytes; the d_work / work_bytes arguments of
+cs_fm_count_device and cs_fm_locate_device, include/cs_fmindex.h) — the path the headline count and the one-call locate bench legs run.
 
 One workspace serves a sequence of calls: counts and one-call locates of
 different batch sizes on the same memory, batches that list long patterns and general
