@@ -38,6 +38,8 @@ QT_LONG_LOADS8, QT_LONG_ROUND2, QT_LONG_BYTE_TEXT, QT_QCTX_UNSTAGED = 1 << 12, 1
 QT_NO_ONEPASS, QT_ONEPASS_SA, QT_LOC_DEFER, QT_LOCATE_U1 = 1 << 16, 1 << 17, 1 << 18, 1 << 19
 QT_WALK_ROWS, QT_WALK_PERSISTENT, QT_GENERAL_INLANE, QT_GENERAL_LIST_ALL = 1 << 20, 1 << 21, 1 << 22, 1 << 23
 QT_MAP_LDS = 1 << 24
+# the largest mismatch bound of count_mismatches (include/cs_fmindex_approx.h CS_MM_MAX)
+CS_MM_MAX = 3
 
 _u8p = C.POINTER(C.c_uint8)
 _u64p = C.POINTER(C.c_uint64)
@@ -110,7 +112,8 @@ class cs_fm_info(C.Structure):
                 ("locate_record_width", C.c_uint64), ("device_bytes", C.c_uint64)]
 
 
-# Every entry point of include/cs_fmindex.h (and cs_fmindex_diag.h, cs_fmindex_replica.h, cs_synth.h)
+# Every entry point of include/cs_fmindex.h (and cs_fmindex_diag.h, cs_fmindex_replica.h,
+# cs_fmindex_approx.h, cs_synth.h)
 # with its ctypes signature.
 SIGNATURES = {
     "cs_default_build_params": (None, [C.POINTER(cs_build_params)]),
@@ -187,6 +190,11 @@ SIGNATURES = {
                                            C.c_int, _vp]),
     # include/cs_fmindex_diag.h (measurement twins; building blocks below)
     "cs_fm_count_bytes_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp]),
+    # include/cs_fmindex_approx.h (count within k mismatches, per distance)
+    "cs_fm_count_mismatch_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_uint32, _vp,
+                                              C.c_uint32, _vp]),
+    "cs_fm_count_mismatch_batch": (C.c_int, [_vp, _u8p, _u64p, C.c_uint64, C.c_uint32, _u64p, _vp]),
+    "cs_fm_count_mismatch": (C.c_int, [_vp, C.c_char_p, C.c_uint64, C.c_uint32, _u64p]),
 }
 
 _lib = None
@@ -463,6 +471,35 @@ class FMIndex:
         out = np.zeros(max(npat, 1), np.uint64)
         _check(lib().cs_fm_count_batch(self._h, _u8(buf), _u64(offs), npat, _u64(out), None))
         return out[:npat]
+
+    # -- within k mismatches, per distance (include/cs_fmindex_approx.h) ----
+    def count_mismatches(self, pattern, k: int) -> np.ndarray:
+        """hist[d], d = 0..k: the summed counts of the strings at Hamming distance d from
+        `pattern` (cs_fm_count_mismatch); hist[0] == count(pattern).  k <= CS_MM_MAX."""
+        b = _bytes(pattern)
+        out = np.zeros(k + 1, np.uint64)
+        _check(lib().cs_fm_count_mismatch(self._h, b, len(b), k, _u64(out)))
+        return out
+
+    def count_mismatches_batch(self, patterns=None, k: int = 1, buf=None, offs=None) -> np.ndarray:
+        """-> uint64 [npat, k + 1], one histogram per pattern (cs_fm_count_mismatch_batch)."""
+        if patterns is not None:
+            buf, offs = pack_patterns(patterns)
+        buf = np.ascontiguousarray(buf, np.uint8)
+        if len(buf) == 0:
+            buf = np.zeros(1, np.uint8)
+        offs = np.ascontiguousarray(offs, np.uint64)
+        npat = len(offs) - 1
+        out = np.zeros((max(npat, 1), k + 1), np.uint64)
+        _check(lib().cs_fm_count_mismatch_batch(self._h, _u8(buf), _u64(offs), npat, k, _u64(out), None))
+        return out[:npat]
+
+    def count_mismatch_device(self, d_pats, d_offs, npat, k, d_hist, fixed_m=0, flags=0, stream=0):
+        """Histograms of a device batch into d_hist (uint64 [npat, k + 1]), asynchronous on
+        `stream` (cs_fm_count_mismatch_device): d_offs or None for npat patterns of length
+        fixed_m back to back; flags Q_* leave structures out (same results)."""
+        _check(lib().cs_fm_count_mismatch_device(self._h, d_pats or None, d_offs or None, fixed_m, npat, k,
+                                                 d_hist, flags, stream or None))
 
     def locate_batch(self, patterns=None, limit: int = 100000, buf=None, offs=None):
         """-> (out_offs[npat+1], positions) with positions of pattern q in row order at

@@ -1057,6 +1057,65 @@ cs_status cs_fm_count(const cs_fm_index* h, const uint8_t* pattern, uint64_t m, 
   return cs_fm_count_batch(h, pattern, offs, 1, out, nullptr);
 }
 
+// ---- count within k mismatches (include/cs_fmindex_approx.h) ----
+static cs_status mismatch_bound_ok(uint32_t k) {
+  if (k > CS_MM_MAX) {
+    set_error("mismatch bound k must be at most CS_MM_MAX = " + std::to_string(CS_MM_MAX));
+    return CS_ERR_INVALID;
+  }
+  return CS_OK;
+}
+
+cs_status cs_fm_count_mismatch_device(const cs_fm_index* h, const uint8_t* d_pats,
+                                      const uint64_t* d_offs, uint64_t fixed_m, uint64_t npat,
+                                      uint32_t k, uint64_t* d_hist, uint32_t flags, void* stream) {
+  DeviceScope dscope;
+  cs_status s = check_handle(h, dscope);
+  if (s != CS_OK) return s;
+  if ((s = mismatch_bound_ok(k)) != CS_OK) return s;
+  if (npat && (!d_hist || (!d_pats && !d_offs && fixed_m))) {
+    set_error("null batch pointer");
+    return CS_ERR_INVALID;
+  }
+  if ((s = null_pats_ok(d_pats, d_offs, npat, (hipStream_t)stream)) != CS_OK) return s;
+  return launch_count_mm(h, d_pats, d_offs, npat, k, d_hist, flags, (hipStream_t)stream,
+                         d_offs ? 0 : fixed_m);
+}
+
+cs_status cs_fm_count_mismatch_batch(const cs_fm_index* h, const uint8_t* pats, const uint64_t* offs,
+                                     uint64_t npat, uint32_t k, uint64_t* out_hist, void* stream) {
+  DeviceScope dscope;
+  cs_status s = check_handle(h, dscope);
+  if (s != CS_OK) return s;
+  if ((s = mismatch_bound_ok(k)) != CS_OK) return s;
+  if (!npat) return CS_OK;
+  if (!offs || !out_hist || (!pats && offs[npat] != offs[0])) {
+    set_error("null batch pointer");
+    return CS_ERR_INVALID;
+  }
+  if ((s = check_offsets(offs, npat)) != CS_OK) return s;
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t out_bytes = npat * (k + 1) * 8;
+  HostPin pin_out;
+  StagedBatch b;
+  if ((s = b.load(h, pats, offs, npat, st)) != CS_OK) return s;
+  StreamBuf d_hist;
+  FMX_HIP(d_hist.alloc(out_bytes, st));
+  pin_out.pin(h, out_hist, out_bytes, st);
+  s = launch_count_mm(h, b.pats.as<uint8_t>(), b.offs.as<uint64_t>(), npat, k, d_hist.as<uint64_t>(), 0,
+                      st, 0);
+  if (s != CS_OK) return s;
+  FMX_HIP(pin_out.copy(out_hist, d_hist.p, out_bytes, false, st));
+  FMX_HIP(hipStreamSynchronize(st));
+  return CS_OK;
+}
+
+cs_status cs_fm_count_mismatch(const cs_fm_index* h, const uint8_t* pattern, uint64_t m, uint32_t k,
+                               uint64_t* out_hist) {
+  const uint64_t offs[2] = {0, m};
+  return cs_fm_count_mismatch_batch(h, pattern, offs, 1, k, out_hist, nullptr);
+}
+
 cs_status cs_fm_locate_check(const cs_fm_index* h, void* stream) {
   DeviceScope dscope;
   cs_status s = check_handle(h, dscope);

@@ -7,6 +7,7 @@
 #include <stdexcept>
 
 #include "../../include/cs_fmindex.h"
+#include "../../include/cs_fmindex_approx.h"
 
 namespace cs {
 namespace {
@@ -136,6 +137,19 @@ std::vector<uint64_t> FMIndex::count_batch(const std::vector<std::string_view>& 
                                   offs.data(), pats.size(), out.data(), nullptr);
   if (s != CS_OK) raise(s);
   return out;
+}
+
+std::vector<uint64_t> FMIndex::count_mismatches(std::string_view pattern, unsigned k) const {
+  if (k > CS_MM_MAX) throw std::invalid_argument("count_mismatches: k must be at most 3");
+  std::vector<uint64_t> hist(k + 1, 0);
+  if (!h_) {  // an empty index, as count()
+    hist[0] = pattern.empty() ? meta_.n : 0;
+    return hist;
+  }
+  cs_status s = cs_fm_count_mismatch(h_.get(), reinterpret_cast<const uint8_t*>(pattern.data()),
+                                     pattern.size(), k, hist.data());
+  if (s != CS_OK) raise(s);
+  return hist;
 }
 
 std::vector<std::vector<uint64_t>> FMIndex::locate_batch(const std::vector<std::string_view>& pats,

@@ -13,6 +13,7 @@
 #include "../../include/cs_fmindex_tuning.h"
 #include "../../include/cs_fmindex_diag.h"
 #include "../../include/cs_fmindex_replica.h"
+#include "../../include/cs_fmindex_approx.h"
 #include "fm_device.hpp"
 
 struct cs_fm_index {
@@ -281,6 +282,10 @@ constexpr uint64_t kPartPad = 64;
 cs_status launch_count_ex(const cs_fm_index* h, const uint8_t* d_pats, const uint64_t* d_offs,
                           uint64_t npat, const fmx::CountOut& co, uint32_t flags, hipStream_t st,
                           uint64_t fixed_m, bool packed, const Work& work = Work{});
+// count within k <= CS_MM_MAX mismatches (cs_fmindex_approx.h): d_hist[npat][k + 1]
+cs_status launch_count_mm(const cs_fm_index* h, const uint8_t* d_pats, const uint64_t* d_offs,
+                          uint64_t npat, uint32_t k, uint64_t* d_hist, uint32_t flags, hipStream_t st,
+                          uint64_t fixed_m);
 cs_status launch_count_one(const cs_fm_index* h, const fmx::OnePattern& p, uint64_t* out_host,
                            hipStream_t st);
 cs_status launch_count_bytes(const cs_fm_index* h, const uint8_t* d_pats, const uint64_t* d_offs,

@@ -55,6 +55,46 @@ __global__ __launch_bounds__(kBlk) void k_count(DevIndex ix, const uint8_t* __re
   store_count<0>(co, q, res);
 }
 
+// Count within k <= K mismatches, per distance (cs_fm_count_mismatch_device): one pattern per
+// lane, hist[q][d] = the summed exact counts of the strings at Hamming distance d from the
+// pattern, d = 0..k, by the depth-first search of mm_frame (fm_search.hpp) — at most K + 1
+// nested frames, all in registers.  Pattern bytes are read by index from global memory (they
+// stay in the caches; no length cap).  K = 1 also serves k = 0, the exact count.  A lane
+// whose tree is small idles until its wave's largest is done.
+template <class E, int K>
+__global__ __launch_bounds__(kBlk) void k_count_mm(DevIndex ix, const uint8_t* __restrict__ pats,
+                                                   const uint64_t* __restrict__ offs, uint64_t npat,
+                                                   uint32_t k, uint64_t* __restrict__ hist,
+                                                   uint64_t fixed_m) {
+  __shared__ NodeTable T;
+  __shared__ SymList L;
+  load_table(T, ix.table);
+  __syncthreads();
+  list_symbols(L, T);
+  const uint64_t q = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  if (q >= npat) return;
+  const uint64_t o0 = offs ? offs[q] : q * fixed_m, m = offs ? offs[q + 1] - o0 : fixed_m;
+  uint64_t h[K + 1];
+#pragma unroll
+  for (int d = 0; d <= K; ++d) h[d] = 0;
+  if (m == 0) {
+    h[0] = ix.n;  // fm_index.cpp:80
+  } else if (ix.n != 0) {  // :81
+    if (K == 1 && k == 0) h[0] = count_pattern<E>(ix, T, pats + o0, m);
+    else {
+      SubPat<K> S;
+      S.b = pats + o0;
+#pragma unroll
+      for (int t = 0; t < K; ++t) S.pos[t] = ~0ull, S.sym[t] = 0;
+      mm_frame<E, 0, K>(ix, T, L, S, m, m, 0, ix.n, h);
+    }
+  }
+  uint64_t* const out = hist + q * (k + 1);
+#pragma unroll
+  for (int d = 0; d <= K; ++d)
+    if ((uint32_t)d <= k) out[d] = h[d];
+}
+
 // The batch count over occurrence lines with left contexts, the C4/C5 shape: a
 // pattern whose last k = ptab_k characters are in the prefix table and whose other
 // m - k <= kCtxQ characters are coded needs two dependent reads — its table entry,
@@ -3994,6 +4034,22 @@ cs_status launch_count_ex(const cs_fm_index* h, const uint8_t* d_pats, const uin
       });
     });
   }
+  FMX_HIP(hipGetLastError());
+  return CS_OK;
+}
+
+cs_status launch_count_mm(const cs_fm_index* h, const uint8_t* d_pats, const uint64_t* d_offs,
+                          uint64_t npat, uint32_t k, uint64_t* d_hist, uint32_t flags, hipStream_t st,
+                          uint64_t fixed_m) {
+  if (!npat) return CS_OK;
+  const DevIndex ix = query_dev(h, call_flags(h, flags));
+  const unsigned g = grid_for(npat, kBlk, 0xFFFFFFFFu);
+  with_engine(h->line_fmt, [&](auto engine) {
+    with_int<2, 3, 1>((int)k, [&](auto K) {  // (k = 0 takes K = 1)
+      using E = typename decltype(engine)::type;
+      k_count_mm<E, K><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, k, d_hist, fixed_m);
+    });
+  });
   FMX_HIP(hipGetLastError());
   return CS_OK;
 }

@@ -155,7 +155,48 @@ struct WM {
     }
     return d;
   }
+  // all children of a range (k_count_mm): nothing shared between symbols, a step per child
+  struct Kids {};
+  __device__ static __forceinline__ void kids(const DevIndex&, const NodeTable&, uint64_t, uint64_t,
+                                              Kids&) {}
+  __device__ static __forceinline__ bool kid(const DevIndex& ix, const NodeTable& T, const Kids&,
+                                             uint32_t c, uint64_t sp, uint64_t ep, uint64_t& csp,
+                                             uint64_t& cep) {
+    csp = sp;
+    cep = ep;
+    return step(ix, T, c, csp, cep);
+  }
 };
+
+// All children of a range over occurrence lines (OccE, LOccE): occ of the four codes at sp
+// and at ep, from one read of each end's line, code 0 already corrected for the rare rows
+// below.  The child of a present symbol c is then [C[c] + lo, C[c] + hi) of its code with no
+// further read; a rare symbol is counted from the LDS list, as in step.
+struct OccKids {
+  uint64_t lo[4], hi[4];
+};
+__device__ __forceinline__ bool occ_kid(const NodeTable& T, const OccKids& k, uint32_t c,
+                                        uint64_t sp, uint64_t ep, uint64_t& csp, uint64_t& cep) {
+  const uint32_t code = T.occ_code[c];
+  uint64_t rs, re;
+  if (code == kNoCode) {
+    rs = exc_rank(T, c, sp);
+    re = exc_rank(T, c, ep);
+  } else {
+    // (masks, not k.lo[code]: an indexed read — and a chain of selects, which the compiler
+    // folds back into one — would move the eight ranges of every frame to scratch)
+    rs = re = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i) {
+      const uint64_t pick = 0ull - (uint64_t)(code == i);
+      rs |= k.lo[i] & pick;
+      re |= k.hi[i] & pick;
+    }
+  }
+  csp = T.C[c] + rs;
+  cep = T.C[c] + re;
+  return csp < cep;
+}
 
 // OccE: occurrence lines (fm_device.hpp OccLine).  occ(c, i) = one line read:
 // base(code) + rows of that code before i in the line, minus the rare-symbol rows
@@ -225,6 +266,29 @@ struct OccE {
     uint64_t r = occ_line(v, code, i);
     if (code == 0) r -= exc_before(T, i);
     return r;
+  }
+  using Kids = OccKids;
+  __device__ static __forceinline__ void kids(const DevIndex& ix, const NodeTable& T, uint64_t sp,
+                                              uint64_t ep, Kids& k) {
+    const uint64_t qa = sp >> 6, qe = ep >> 6;
+    OccLine::Raw va;
+    OccLine::load(ix.lines, qa, va);
+    OccLine::Raw ve = {va[0], va[1]};
+    if (qe != qa) OccLine::load(ix.lines, qe, ve);  // sp and ep in one line: one read
+    // (written out, not a loop: constant indices from the start keep the ranges in registers)
+    k.lo[0] = occ_line(va, 0, sp), k.hi[0] = occ_line(ve, 0, ep);
+    k.lo[1] = occ_line(va, 1, sp), k.hi[1] = occ_line(ve, 1, ep);
+    k.lo[2] = occ_line(va, 2, sp), k.hi[2] = occ_line(ve, 2, ep);
+    k.lo[3] = occ_line(va, 3, sp), k.hi[3] = occ_line(ve, 3, ep);
+    if (T.exc_n) {
+      k.lo[0] -= exc_before(T, sp);
+      k.hi[0] -= exc_before(T, ep);
+    }
+  }
+  __device__ static __forceinline__ bool kid(const DevIndex&, const NodeTable& T, const Kids& k,
+                                             uint32_t c, uint64_t sp, uint64_t ep, uint64_t& csp,
+                                             uint64_t& cep) {
+    return occ_kid(T, k, c, sp, ep, csp, cep);
   }
 };
 
@@ -312,6 +376,28 @@ struct LOccE {
     if (code == 0) r -= exc_before(T, i);
     return r;
   }
+  using Kids = OccKids;
+  __device__ static __forceinline__ void kids(const DevIndex& ix, const NodeTable& T, uint64_t sp,
+                                              uint64_t ep, Kids& k) {
+    const uint64_t qa = line_of(sp), qe = line_of(ep);
+    LOccLine::Raw va;
+    LOccLine::load(ix.lines, qa, va);
+    LOccLine::Raw ve = {va[0], va[1]};
+    if (qe != qa) LOccLine::load(ix.lines, qe, ve);
+    k.lo[0] = occ_line(ix, va, 0, qa, sp), k.hi[0] = occ_line(ix, ve, 0, qe, ep);
+    k.lo[1] = occ_line(ix, va, 1, qa, sp), k.hi[1] = occ_line(ix, ve, 1, qe, ep);
+    k.lo[2] = occ_line(ix, va, 2, qa, sp), k.hi[2] = occ_line(ix, ve, 2, qe, ep);
+    k.lo[3] = occ_line(ix, va, 3, qa, sp), k.hi[3] = occ_line(ix, ve, 3, qe, ep);
+    if (T.exc_n) {
+      k.lo[0] -= exc_before(T, sp);
+      k.hi[0] -= exc_before(T, ep);
+    }
+  }
+  __device__ static __forceinline__ bool kid(const DevIndex&, const NodeTable& T, const Kids& k,
+                                             uint32_t c, uint64_t sp, uint64_t ep, uint64_t& csp,
+                                             uint64_t& cep) {
+    return occ_kid(T, k, c, sp, ep, csp, cep);
+  }
 };
 
 // QWM: quaternary wavelet matrix over dense symbol codes, for alphabets beyond the
@@ -393,6 +479,17 @@ struct QWM {
     uint64_t sp = 0, ep = i;
     (void)step(ix, T, c, sp, ep);
     return ep - sp;
+  }
+  // all children of a range (k_count_mm): a step per child, as WM
+  struct Kids {};
+  __device__ static __forceinline__ void kids(const DevIndex&, const NodeTable&, uint64_t, uint64_t,
+                                              Kids&) {}
+  __device__ static __forceinline__ bool kid(const DevIndex& ix, const NodeTable& T, const Kids&,
+                                             uint32_t c, uint64_t sp, uint64_t ep, uint64_t& csp,
+                                             uint64_t& cep) {
+    csp = sp;
+    cep = ep;
+    return step(ix, T, c, csp, cep);
   }
 };
 
@@ -646,6 +743,26 @@ __device__ __forceinline__ uint64_t pat8(BytePat P, uint64_t j, uint64_t k) {
   for (uint32_t i = 0; i < 8 && j + i < k; ++i) x |= (uint64_t)P[j + i] << (8 * i);
   return x;
 }
+// A pattern with up to K of its bytes substituted (k_count_mm: the neighbour a leaf frame
+// stands for): byte pos[t] reads sym[t]; an unused slot has pos = ~0.
+template <int K>
+struct SubPat {
+  const uint8_t* b;
+  uint64_t pos[K];
+  uint32_t sym[K];
+  __device__ __forceinline__ uint32_t operator[](uint64_t i) const {
+    uint32_t c = b[i];
+#pragma unroll
+    for (int t = 0; t < K; ++t) c = i == pos[t] ? sym[t] : c;
+    return c;
+  }
+};
+template <int K>
+__device__ __forceinline__ uint64_t pat8(const SubPat<K>& P, uint64_t j, uint64_t k) {
+  uint64_t x = 0;
+  for (uint32_t i = 0; i < 8 && j + i < k; ++i) x |= (uint64_t)P[j + i] << (8 * i);
+  return x;
+}
 // the mask of the bytes of a chunk at j that lie inside P[0, k)
 __device__ __forceinline__ uint64_t chunk_mask(uint64_t j, uint64_t k) {
   return k - j >= 8 ? ~0ull : (1ull << (8 * (k - j))) - 1;
@@ -757,6 +874,17 @@ __device__ __forceinline__ uint32_t verify_filter(const DevIndex& ix, PT P, uint
 // P[s, ...) as a pattern of its own
 __device__ __forceinline__ const uint8_t* pat_shift(const uint8_t* P, uint64_t s) { return P + s; }
 __device__ __forceinline__ BytePat pat_shift(BytePat P, uint64_t s) { return BytePat{P.b + s}; }
+template <int K>
+__device__ __forceinline__ SubPat<K> pat_shift(const SubPat<K>& P, uint64_t s) {
+  SubPat<K> r;
+  r.b = P.b + s;
+#pragma unroll
+  for (int t = 0; t < K; ++t) {
+    r.pos[t] = P.pos[t] - s;  // (a position below s wraps far past every index read)
+    r.sym[t] = P.sym[t];
+  }
+  return r;
+}
 __device__ __forceinline__ PackedDna pat_shift(PackedDna P, uint64_t s) {
   return PackedDna{s < 32 ? P.x >> (2 * s) : 0ull};
 }
@@ -824,6 +952,105 @@ __device__ __forceinline__ uint64_t count_rest(const DevIndex& ix, const NodeTab
     if (!E::step(ix, T, P[k], sp, ep, bytes)) return 0;
   }
   return ep - sp;
+}
+
+// ---- count within k mismatches (k_count_mm; include/cs_fmindex_approx.h) ----
+// The substitute alphabet: the symbols present in the text (C[c] < C[c+1]), ascending, listed
+// once per block.  Every thread of a kBlk block calls list_symbols after the node table is
+// staged; it ends with a barrier.
+struct SymList {
+  uint8_t sym[256];
+  uint32_t n;
+  uint32_t wave[kBlk / 64];
+};
+__device__ __forceinline__ void list_symbols(SymList& L, const NodeTable& T) {
+  static_assert(kBlk == 256, "one symbol per thread");
+  const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const bool present = T.C[t] < T.C[t + 1];
+  const uint64_t bal = __ballot(present);
+  if (lane == 0) L.wave[wv] = (uint32_t)__popcll(bal);
+  __syncthreads();
+  uint32_t before = 0, all = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < kBlk / 64; ++w) {
+    if (w < wv) before += L.wave[w];
+    all += L.wave[w];
+  }
+  if (present) L.sym[before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = (uint8_t)t;
+  if (t == 0) L.n = all;
+  __syncthreads();
+}
+
+// One frame of the depth-first search: D mismatches spent (S: the pattern P = S.b with the D
+// substitutions of the frames above), P[0..j) still to consume from the
+// non-empty range [sp, ep) (frame 0 starts at j = m with the whole index and takes its first
+// ranges from C[], fm_index.cpp:84-89).  The frame walks the exact path downwards; at each
+// position it descends, for every present symbol s != P[j-1] whose range is not empty, into
+// frame D + 1 at position j - 1, and that child is exhausted before this frame resumes.  A
+// frame that reaches j = 0 adds its range to hist[D].  Frame K does no branching: it is the
+// rest of an exact count (count_rest: the plain steps, or the left contexts / the text where
+// the index has them and the call's flags allow; or the neighbour's own count from the
+// prefix table, below).  An empty range prunes at once, exactly where the reference returns 0.
+// The frames are the nested instances of this template (K is a compile-time constant, every
+// call is inlined), so a frame's state — j, the range, the children's ranges and the symbol
+// cursor — lives in registers and no stack exists.
+template <class E, int D, int K>
+__device__ __forceinline__ void mm_frame(const DevIndex& ix, const NodeTable& T, const SymList& L,
+                                         const SubPat<K>& S, uint64_t m, uint64_t j, uint64_t sp,
+                                         uint64_t ep, uint64_t (&hist)[K + 1]) {
+  const uint8_t* const P = S.b;
+  if constexpr (D == K) {
+    // The neighbour S is fixed from here.  While fewer characters than the prefix table's
+    // are consumed, its count starts over from the table entry of S's own last characters
+    // (one read in place of the steps still missing to that depth, count_pattern); else it
+    // goes on from [sp, ep), where P[0..j) is S's rest.
+    bool restart = ix.ptab_k && m >= ix.ptab_k && m - j < ix.ptab_k;
+#pragma unroll
+    for (int t = 0; t < K; ++t) restart &= T.code[S.sym[t]] != kNoCode;
+    if (restart) hist[D] += count_pattern<E>(ix, T, S, m);
+    else hist[D] += count_rest<E, const uint8_t*, false>(ix, T, P, j, sp, ep, nullptr, nullptr);
+  } else {
+    // Bound: j only decreases, so this frame runs at most m iterations.
+    while (j > 0) {
+      const uint32_t c = P[j - 1];
+      const bool top = D == 0 && j == m;
+      typename E::Kids kd;
+      if (!top) E::kids(ix, T, sp, ep, kd);
+      // Bound: the symbol cursor i only increases, at most L.n <= 256 iterations; a child
+      // runs at depth D + 1 <= K with j - 1 characters, so the whole tree of a pattern has
+      // at most (256 m)^K m nodes whatever the pattern bytes are.
+      for (uint32_t i = 0; i < L.n; ++i) {
+        const uint32_t s = L.sym[i];
+        if (s == c) continue;
+        uint64_t csp, cep;
+        bool live = true;
+        if (top) {
+          csp = T.C[s];
+          cep = T.C[s + 1];
+        } else {
+          live = E::kid(ix, T, kd, s, sp, ep, csp, cep);
+        }
+        if (live) {
+          SubPat<K> child = S;
+          child.pos[D] = j - 1;
+          child.sym[D] = s;
+          mm_frame<E, D + 1, K>(ix, T, L, child, m, j - 1, csp, cep, hist);
+        }
+      }
+      if (T.C[c] == T.C[c + 1]) return;  // symbol absent: every longer exact path counts 0
+      if (top) {
+        sp = T.C[c];
+        ep = T.C[c + 1];
+      } else {
+        uint64_t nsp, nep;
+        if (!E::kid(ix, T, kd, c, sp, ep, nsp, nep)) return;
+        sp = nsp;
+        ep = nep;
+      }
+      --j;
+    }
+    hist[D] += ep - sp;
+  }
 }
 
 // Locate records (phase 1 -> phase 2, cs_fm_locate_ranges_device's d_sp): the

@@ -4,7 +4,7 @@
 // exceptions as cs::FMIndex (src/api/fm_index.hpp:11-67); the work runs on the GPU
 // through the C ABI in cs_fmindex.h (implementation: csrc/fm_facade.cpp inside
 // libcs_fmindex.so).  Additions: count_batch / locate_batch (one launch for many
-// patterns), save_directory (the on-disk format open_directory reads), handle()
+// patterns), count_mismatches (occurrences within k substitutions), save_directory (the on-disk format open_directory reads), handle()
 // for the raw ABI, borrow() to wrap an ABI handle and serve() (resident
 // single-pattern server).  Errors are
 // std::runtime_error with the reference's message text ("locate: LF walk exceeded
@@ -52,6 +52,10 @@ class FMIndex {
   std::vector<uint64_t> count_batch(const std::vector<std::string_view>& patterns) const;
   std::vector<std::vector<uint64_t>> locate_batch(const std::vector<std::string_view>& patterns,
                                                   size_t limit = 100000) const;
+  // Occurrences within k <= 3 substitutions, per distance (cs_fmindex_approx.h): k + 1
+  // values, [d] = the summed counts of the strings at Hamming distance d from the pattern.
+  // Throws std::invalid_argument for k > 3.
+  std::vector<uint64_t> count_mismatches(std::string_view pattern, unsigned k) const;
 
   // Serving mode for single-pattern count(): a resident wave answers from a pinned
   // mailbox instead of one kernel launch per call (cs_fm_serve_start / _stop).
