@@ -113,7 +113,7 @@ class cs_fm_info(C.Structure):
 
 
 # Every entry point of include/cs_fmindex.h (and cs_fmindex_diag.h, cs_fmindex_replica.h,
-# cs_fmindex_approx.h, cs_synth.h)
+# cs_fmindex_approx.h, cs_fmindex_approx_locate.h, cs_synth.h)
 # with its ctypes signature.
 SIGNATURES = {
     "cs_default_build_params": (None, [C.POINTER(cs_build_params)]),
@@ -190,11 +190,21 @@ SIGNATURES = {
                                            C.c_int, _vp]),
     # include/cs_fmindex_diag.h (measurement twins; building blocks below)
     "cs_fm_count_bytes_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp]),
+    "cs_fm_locate_mismatch_phases_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_uint32, _vp,
+                                                      _vp, _vp, C.c_uint64, _u64p, C.c_uint32,
+                                                      C.POINTER(C.c_float), _vp]),
     # include/cs_fmindex_approx.h (count within k mismatches, per distance)
     "cs_fm_count_mismatch_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_uint32, _vp,
                                               C.c_uint32, _vp]),
     "cs_fm_count_mismatch_batch": (C.c_int, [_vp, _u8p, _u64p, C.c_uint64, C.c_uint32, _u64p, _vp]),
     "cs_fm_count_mismatch": (C.c_int, [_vp, C.c_char_p, C.c_uint64, C.c_uint32, _u64p]),
+    # include/cs_fmindex_approx_locate.h (positions within k mismatches, with distances)
+    "cs_fm_locate_mismatch_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_uint32, _vp, _vp,
+                                               _vp, C.c_uint64, _u64p, C.c_uint32, _vp]),
+    "cs_fm_locate_mismatch_batch": (C.c_int, [_vp, _u8p, _u64p, C.c_uint64, C.c_uint32, _u64p, _u64p,
+                                              _u8p, C.c_uint64, _u64p, _vp]),
+    "cs_fm_locate_mismatch": (C.c_int, [_vp, C.c_char_p, C.c_uint64, C.c_uint32, _u64p, _u8p,
+                                        C.c_uint64, _u64p]),
 }
 
 _lib = None
@@ -500,6 +510,60 @@ class FMIndex:
         fixed_m back to back; flags Q_* leave structures out (same results)."""
         _check(lib().cs_fm_count_mismatch_device(self._h, d_pats or None, d_offs or None, fixed_m, npat, k,
                                                  d_hist, flags, stream or None))
+
+    # -- positions within k mismatches (include/cs_fmindex_approx_locate.h) ----
+    def locate_mismatches(self, pattern, k: int):
+        """-> (pos uint64[], dist uint8[]): every position at Hamming distance dist <= k from
+        `pattern`, in the search's order (cs_fm_locate_mismatch).  k <= CS_MM_MAX."""
+        _, pos, dist = self.locate_mismatches_batch([_bytes(pattern)], k)
+        return pos, dist
+
+    def locate_mismatches_batch(self, patterns=None, k: int = 1, buf=None, offs=None):
+        """-> (out_offs[npat + 1], pos, dist): the pairs of pattern q at
+        [out_offs[q], out_offs[q + 1]) (cs_fm_locate_mismatch_batch; a first call sizes the
+        output)."""
+        if patterns is not None:
+            buf, offs = pack_patterns(patterns)
+        buf = np.ascontiguousarray(buf, np.uint8)
+        if len(buf) == 0:
+            buf = np.zeros(1, np.uint8)
+        offs = np.ascontiguousarray(offs, np.uint64)
+        npat = len(offs) - 1
+        out_offs = np.zeros(npat + 1, np.uint64)
+        total = C.c_uint64()
+        st = lib().cs_fm_locate_mismatch_batch(self._h, _u8(buf), _u64(offs), npat, k, _u64(out_offs),
+                                               None, None, 0, C.byref(total), None)
+        if st == CS_OK:
+            return out_offs, np.zeros(0, np.uint64), np.zeros(0, np.uint8)
+        if st != CS_ERR_CAPACITY:
+            _check(st)
+        pos = np.zeros(total.value, np.uint64)
+        dist = np.zeros(total.value, np.uint8)
+        _check(lib().cs_fm_locate_mismatch_batch(self._h, _u8(buf), _u64(offs), npat, k, _u64(out_offs),
+                                                 _u64(pos), _u8(dist), total.value, C.byref(total), None))
+        return out_offs, pos, dist
+
+    def locate_mismatch_device(self, d_pats, d_offs, npat, k, d_out_offs, d_out_pos, d_out_dist, cap,
+                               fixed_m=0, flags=0, stream=0, phase_ms=None):
+        """Positions and distances of a device batch (cs_fm_locate_mismatch_device): offsets
+        into d_out_offs[npat + 1] and, when the total fits `cap`, d_out_pos / d_out_dist
+        -> (total, written).  d_offs or None for npat patterns of length fixed_m back to
+        back; cap = 0 with null outputs sizes; flags Q_* leave structures out (same results).
+        phase_ms: a list that receives the five phase times of the measurement twin
+        (cs_fm_locate_mismatch_phases_device)."""
+        total = C.c_uint64()
+        args = (self._h, d_pats or None, d_offs or None, fixed_m, npat, k, d_out_offs, d_out_pos or None,
+                d_out_dist or None, cap, C.byref(total), flags)
+        if phase_ms is None:
+            st = lib().cs_fm_locate_mismatch_device(*args, stream or None)
+        else:
+            ms = (C.c_float * 5)()
+            st = lib().cs_fm_locate_mismatch_phases_device(*args, ms, stream or None)
+            phase_ms[:] = list(ms)
+        if st == CS_ERR_CAPACITY:
+            return total.value, False
+        _check(st)
+        return total.value, True
 
     def locate_batch(self, patterns=None, limit: int = 100000, buf=None, offs=None):
         """-> (out_offs[npat+1], positions) with positions of pattern q in row order at

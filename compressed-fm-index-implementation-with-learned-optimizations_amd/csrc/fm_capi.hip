@@ -1116,6 +1116,159 @@ cs_status cs_fm_count_mismatch(const cs_fm_index* h, const uint8_t* pattern, uin
   return cs_fm_count_mismatch_batch(h, pattern, offs, 1, k, out_hist, nullptr);
 }
 
+// ---- locate within k mismatches (include/cs_fmindex_approx_locate.h) ----
+// the device batch; phase_ms: null, or the five phase times of cs_fm_locate_mismatch_phases_device
+static cs_status locate_mismatch_device(const cs_fm_index* h, const uint8_t* d_pats,
+                                        const uint64_t* d_offs, uint64_t fixed_m, uint64_t npat,
+                                        uint32_t k, uint64_t* d_out_offs, uint64_t* d_out_pos,
+                                        uint8_t* d_out_dist, uint64_t cap, uint64_t* total,
+                                        uint32_t flags, hipStream_t st, float* phase_ms) {
+  DeviceScope dscope;
+  cs_status s = check_handle(h, dscope);
+  if (s != CS_OK) return s;
+  if ((s = mismatch_bound_ok(k)) != CS_OK) return s;
+  if (!total || !d_out_offs || (cap && (!d_out_pos || !d_out_dist)) ||
+      (npat && !d_pats && !d_offs && fixed_m)) {
+    set_error("null batch pointer");
+    return CS_ERR_INVALID;
+  }
+  if ((s = null_pats_ok(d_pats, d_offs, npat, st)) != CS_OK) return s;
+  struct Events {
+    hipEvent_t e[6] = {};
+    ~Events() {
+      for (hipEvent_t x : e)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } ev;
+  if (phase_ms) {
+    for (int i = 0; i < 5; ++i) phase_ms[i] = 0.f;
+    for (hipEvent_t& x : ev.e) FMX_HIP(hipEventCreate(&x));
+  }
+  hipEvent_t* e = phase_ms ? ev.e : nullptr;
+  MmLeafPlan plan;
+  const uint64_t fm = d_offs ? 0 : fixed_m;
+  if ((s = launch_locate_mm_size(h, d_pats, d_offs, npat, k, fm, d_out_offs, flags, st, plan, e)) != CS_OK)
+    return s;
+  *total = plan.total;
+  if (phase_ms) {
+    FMX_HIP(hipEventElapsedTime(&phase_ms[0], e[0], e[1]));
+    FMX_HIP(hipEventElapsedTime(&phase_ms[1], e[1], e[2]));
+  }
+  if (plan.total > cap) {
+    set_error("locate: capacity too small");
+    return CS_ERR_CAPACITY;
+  }
+  if (!plan.total) return CS_OK;
+  s = launch_locate_mm_emit(h, d_pats, d_offs, npat, k, fm, d_out_offs, plan, d_out_pos, d_out_dist, flags,
+                            st, e);
+  if (s != CS_OK) return s;
+  if (phase_ms) {  // (the emitting step has synchronised: its events are complete)
+    FMX_HIP(hipEventElapsedTime(&phase_ms[2], e[2], e[3]));
+    FMX_HIP(hipEventElapsedTime(&phase_ms[3], e[3], e[4]));
+    FMX_HIP(hipEventElapsedTime(&phase_ms[4], e[4], e[5]));
+  }
+  return CS_OK;
+}
+
+cs_status cs_fm_locate_mismatch_device(const cs_fm_index* h, const uint8_t* d_pats,
+                                       const uint64_t* d_offs, uint64_t fixed_m, uint64_t npat,
+                                       uint32_t k, uint64_t* d_out_offs, uint64_t* d_out_pos,
+                                       uint8_t* d_out_dist, uint64_t cap, uint64_t* total,
+                                       uint32_t flags, void* stream) {
+  return locate_mismatch_device(h, d_pats, d_offs, fixed_m, npat, k, d_out_offs, d_out_pos, d_out_dist, cap,
+                                total, flags, (hipStream_t)stream, nullptr);
+}
+
+cs_status cs_fm_locate_mismatch_phases_device(const cs_fm_index* h, const uint8_t* d_pats,
+                                              const uint64_t* d_offs, uint64_t fixed_m, uint64_t npat,
+                                              uint32_t k, uint64_t* d_out_offs, uint64_t* d_out_pos,
+                                              uint8_t* d_out_dist, uint64_t cap, uint64_t* total,
+                                              uint32_t flags, float* phase_ms, void* stream) {
+  if (!phase_ms) {
+    set_error("null phase_ms");
+    return CS_ERR_INVALID;
+  }
+  return locate_mismatch_device(h, d_pats, d_offs, fixed_m, npat, k, d_out_offs, d_out_pos, d_out_dist, cap,
+                                total, flags, (hipStream_t)stream, phase_ms);
+}
+
+cs_status cs_fm_locate_mismatch_batch(const cs_fm_index* h, const uint8_t* pats, const uint64_t* offs,
+                                      uint64_t npat, uint32_t k, uint64_t* out_offs, uint64_t* out_pos,
+                                      uint8_t* out_dist, uint64_t cap, uint64_t* total, void* stream) {
+  DeviceScope dscope;
+  cs_status s = check_handle(h, dscope);
+  if (s != CS_OK) return s;
+  if ((s = mismatch_bound_ok(k)) != CS_OK) return s;
+  if (!total || !out_offs) {
+    set_error("null batch pointer");
+    return CS_ERR_INVALID;
+  }
+  *total = 0;
+  if (!npat) {
+    out_offs[0] = 0;
+    return CS_OK;
+  }
+  if (!offs || (!pats && offs[npat] != offs[0])) {
+    set_error("null batch pointer");
+    return CS_ERR_INVALID;
+  }
+  if ((s = check_offsets(offs, npat)) != CS_OK) return s;
+  hipStream_t st = (hipStream_t)stream;
+  StagedBatch b;
+  if ((s = b.load(h, pats, offs, npat, st)) != CS_OK) return s;
+  StreamBuf d_oo;
+  FMX_HIP(d_oo.alloc((npat + 1) * 8, st));
+  MmLeafPlan plan;
+  if ((s = launch_locate_mm_size(h, b.pats.as<uint8_t>(), b.offs.as<uint64_t>(), npat, k, 0,
+                                 d_oo.as<uint64_t>(), 0, st, plan)) != CS_OK)
+    return s;
+  *total = plan.total;
+  {
+    HostPin po;
+    po.pin(h, out_offs, (npat + 1) * 8, st);
+    FMX_HIP(po.copy(out_offs, d_oo.p, (npat + 1) * 8, false, st));
+  }
+  FMX_HIP(hipStreamSynchronize(st));
+  if (plan.total > cap) {  // after the sizing step: the position phase does not run
+    set_error("locate output capacity too small");
+    return CS_ERR_CAPACITY;
+  }
+  if (!plan.total) return CS_OK;
+  if (!out_pos || !out_dist) {
+    set_error("null output buffer");
+    return CS_ERR_INVALID;
+  }
+  StreamBuf d_pos, d_dist;
+  FMX_HIP(d_pos.alloc(plan.total * 8, st));
+  FMX_HIP(d_dist.alloc(plan.total, st));
+  s = launch_locate_mm_emit(h, b.pats.as<uint8_t>(), b.offs.as<uint64_t>(), npat, k, 0,
+                            d_oo.as<uint64_t>(), plan, d_pos.as<uint64_t>(), d_dist.as<uint8_t>(), 0, st);
+  if (s != CS_OK) return s;
+  HostPin pp, pd;
+  pp.pin(h, out_pos, plan.total * 8, st);
+  pd.pin(h, out_dist, plan.total, st);
+  FMX_HIP(pp.copy(out_pos, d_pos.p, plan.total * 8, false, st));
+  FMX_HIP(pd.copy(out_dist, d_dist.p, plan.total, false, st));
+  FMX_HIP(hipStreamSynchronize(st));
+  return CS_OK;
+}
+
+cs_status cs_fm_locate_mismatch(const cs_fm_index* h, const uint8_t* pattern, uint64_t m, uint32_t k,
+                                uint64_t* out_pos, uint8_t* out_dist, uint64_t cap, uint64_t* nout) {
+  if (!nout) {
+    set_error("null nout");
+    return CS_ERR_INVALID;
+  }
+  *nout = 0;
+  const uint64_t offs[2] = {0, m};
+  uint64_t oo[2] = {0, 0};
+  uint64_t total = 0;
+  cs_status s = cs_fm_locate_mismatch_batch(h, pattern, offs, 1, k, oo, out_pos, out_dist, cap, &total,
+                                            nullptr);
+  *nout = total;
+  return s;
+}
+
 cs_status cs_fm_locate_check(const cs_fm_index* h, void* stream) {
   DeviceScope dscope;
   cs_status s = check_handle(h, dscope);

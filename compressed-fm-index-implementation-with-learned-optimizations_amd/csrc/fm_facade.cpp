@@ -8,6 +8,7 @@
 
 #include "../../include/cs_fmindex.h"
 #include "../../include/cs_fmindex_approx.h"
+#include "../../include/cs_fmindex_approx_locate.h"
 
 namespace cs {
 namespace {
@@ -150,6 +151,25 @@ std::vector<uint64_t> FMIndex::count_mismatches(std::string_view pattern, unsign
                                      pattern.size(), k, hist.data());
   if (s != CS_OK) raise(s);
   return hist;
+}
+
+std::vector<std::pair<uint64_t, uint8_t>> FMIndex::locate_mismatches(std::string_view pattern,
+                                                                     unsigned k) const {
+  if (k > CS_MM_MAX) throw std::invalid_argument("locate_mismatches: k must be at most 3");
+  std::vector<std::pair<uint64_t, uint8_t>> res;
+  if (!h_ || pattern.empty()) return res;  // an empty index or pattern, as locate()
+  const uint8_t* p = reinterpret_cast<const uint8_t*>(pattern.data());
+  uint64_t total = 0;
+  cs_status s = cs_fm_locate_mismatch(h_.get(), p, pattern.size(), k, nullptr, nullptr, 0, &total);
+  if (s != CS_OK && s != CS_ERR_CAPACITY) raise(s);
+  if (!total) return res;
+  std::vector<uint64_t> pos(total);
+  std::vector<uint8_t> dist(total);
+  s = cs_fm_locate_mismatch(h_.get(), p, pattern.size(), k, pos.data(), dist.data(), total, &total);
+  if (s != CS_OK) raise(s);
+  res.reserve(total);
+  for (uint64_t i = 0; i < total; ++i) res.emplace_back(pos[i], dist[i]);
+  return res;
 }
 
 std::vector<std::vector<uint64_t>> FMIndex::locate_batch(const std::vector<std::string_view>& pats,

@@ -14,6 +14,7 @@
 #include "../../include/cs_fmindex_diag.h"
 #include "../../include/cs_fmindex_replica.h"
 #include "../../include/cs_fmindex_approx.h"
+#include "../../include/cs_fmindex_approx_locate.h"
 #include "fm_device.hpp"
 
 struct cs_fm_index {
@@ -417,5 +418,27 @@ inline unsigned grid_for(uint64_t work, unsigned block, unsigned cap = 1u << 20)
   if (g > cap) g = cap;
   return (unsigned)g;
 }
+
+// Locate within k <= CS_MM_MAX mismatches (cs_fmindex_approx_locate.h), in two steps with the
+// caller's capacity check between them.  Sizing: the first traversal and the two scans;
+// d_out_offs[npat + 1] is written, plan.total / plan.nleaf are read back (synchronises st).
+// Emitting: the second traversal into the leaf list, launch_locate_walk over the leaves into
+// d_out_pos[plan.total], the distances into d_out_dist[plan.total], then the overrun word is
+// read (synchronises st; CS_ERR_LF_OVERRUN as the exact locate).  ev: null, or six events
+// recorded at the start and after the sizing traversal, the scans with their read-back, the
+// emitting traversal, the positions and the distances (the benchmark's split).
+struct MmLeafPlan {
+  StreamBuf leaf_base;  // [npat + 1]: the exclusive scan of the patterns' leaf counts
+  uint64_t nleaf = 0, total = 0;
+};
+cs_status launch_locate_mm_size(const cs_fm_index* h, const uint8_t* d_pats, const uint64_t* d_offs,
+                                uint64_t npat, uint32_t k, uint64_t fixed_m, uint64_t* d_out_offs,
+                                uint32_t flags, hipStream_t st, MmLeafPlan& plan,
+                                hipEvent_t* ev = nullptr);
+cs_status launch_locate_mm_emit(const cs_fm_index* h, const uint8_t* d_pats, const uint64_t* d_offs,
+                                uint64_t npat, uint32_t k, uint64_t fixed_m,
+                                const uint64_t* d_out_offs, const MmLeafPlan& plan,
+                                uint64_t* d_out_pos, uint8_t* d_out_dist, uint32_t flags,
+                                hipStream_t st, hipEvent_t* ev = nullptr);
 
 }  // namespace fmx

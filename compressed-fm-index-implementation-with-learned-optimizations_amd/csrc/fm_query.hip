@@ -95,6 +95,81 @@ __global__ __launch_bounds__(kBlk) void k_count_mm(DevIndex ix, const uint8_t* _
     if ((uint32_t)d <= k) out[d] = h[d];
 }
 
+// Locate within k <= K mismatches (cs_fm_locate_mismatch_device): one pattern per lane, the
+// traversal of mm_leaves (fm_search.hpp; k_count_mm's search with a leaf sink), run twice.
+// Sizing (kEmit = false): cnt_leaf[q] / cnt_occ[q] = the pattern's non-empty leaf ranges and
+// the sum of their lengths (slot npat of both is zeroed for the scans' totals).  Emitting
+// (kEmit = true; cnt_leaf / cnt_occ now hold the exclusive scans, the second being the call's
+// d_out_offs): leaf l, in traversal order from the pattern's first leaf, gets leaf_sp[l] (its
+// first row: a plain locate record, bit 63 clear), leaf_off[l] (its offset in the output) and
+// leaf_dist[l]; the thread after the last pattern writes the closing leaf_off[nleaf] = total.
+// A lane never writes at or past its pattern's leaf end, whatever the second traversal does
+// (LeafSink::leaf).  The leaves are then the "patterns" of launch_locate_walk.  An empty
+// pattern has no leaf (fm_index.cpp:109), nor has any pattern over an empty text.
+template <class E, int K, bool kEmit>
+__global__ __launch_bounds__(kBlk) void k_locate_mm(DevIndex ix, const uint8_t* __restrict__ pats,
+                                                    const uint64_t* __restrict__ offs, uint64_t npat,
+                                                    uint32_t k, uint64_t fixed_m, uint64_t* cnt_leaf,
+                                                    uint64_t* cnt_occ, uint64_t* __restrict__ leaf_sp,
+                                                    uint64_t* __restrict__ leaf_off,
+                                                    uint8_t* __restrict__ leaf_dist, uint64_t nleaf,
+                                                    uint64_t total) {
+  __shared__ NodeTable T;
+  __shared__ SymList L;
+  load_table(T, ix.table);
+  __syncthreads();
+  list_symbols(L, T);
+  const uint64_t q = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  if (q > npat) return;
+  if (q == npat) {
+    if (kEmit) leaf_off[nleaf] = total;
+    else cnt_leaf[q] = cnt_occ[q] = 0;  // scan slots for the totals
+    return;
+  }
+  const uint64_t o0 = offs ? offs[q] : q * fixed_m, m = offs ? offs[q + 1] - o0 : fixed_m;
+  LeafSink sink;
+  sink.nleaf = kEmit ? cnt_leaf[q] : 0;
+  sink.nocc = kEmit ? cnt_occ[q] : 0;
+  sink.end = kEmit ? cnt_leaf[q + 1] : 0;
+  sink.leaf_sp = kEmit ? leaf_sp : nullptr;
+  sink.leaf_off = leaf_off;
+  sink.leaf_dist = leaf_dist;
+  if (m != 0 && ix.n != 0) mm_leaves<E, 0, K>(ix, T, L, pats + o0, m, k, m, 0, ix.n, sink);
+  if (!kEmit) {
+    cnt_leaf[q] = sink.nleaf;
+    cnt_occ[q] = sink.nocc;
+  }
+}
+
+// d_out_dist[leaf_off[l] .. leaf_off[l + 1]) = leaf_dist[l].  A lane fills a leaf of at most
+// kLocSmall occurrences; the block's wider leaves (a 1-mer's holds n / 4 rows) are listed in
+// LDS and filled by the whole block, one after the other.
+__global__ __launch_bounds__(kBlk) void k_expand_dist(const uint64_t* __restrict__ leaf_off,
+                                                      const uint8_t* __restrict__ leaf_dist,
+                                                      uint64_t nleaf, uint8_t* __restrict__ out) {
+  __shared__ uint32_t s_wide[kBlk];
+  __shared__ uint32_t s_n;
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  const uint64_t l0 = blockIdx.x * (uint64_t)blockDim.x, l = l0 + threadIdx.x;
+  if (l < nleaf) {
+    const uint64_t a = leaf_off[l], b = leaf_off[l + 1];
+    if (b - a <= kLocSmall) {
+      const uint8_t d = leaf_dist[l];
+      for (uint64_t i = a; i < b; ++i) out[i] = d;
+    } else {
+      s_wide[atomicAdd(&s_n, 1u)] = threadIdx.x;
+    }
+  }
+  __syncthreads();
+  const uint32_t nw = s_n;  // <= kBlk
+  for (uint32_t e = 0; e < nw; ++e) {
+    const uint64_t w = l0 + s_wide[e], a = leaf_off[w], b = leaf_off[w + 1];
+    const uint8_t d = leaf_dist[w];
+    for (uint64_t i = a + threadIdx.x; i < b; i += blockDim.x) out[i] = d;
+  }
+}
+
 // The batch count over occurrence lines with left contexts, the C4/C5 shape: a
 // pattern whose last k = ptab_k characters are in the prefix table and whose other
 // m - k <= kCtxQ characters are coded needs two dependent reads — its table entry,
@@ -4052,6 +4127,82 @@ cs_status launch_count_mm(const cs_fm_index* h, const uint8_t* d_pats, const uin
   });
   FMX_HIP(hipGetLastError());
   return CS_OK;
+}
+
+cs_status launch_locate_mm_size(const cs_fm_index* h, const uint8_t* d_pats, const uint64_t* d_offs,
+                                uint64_t npat, uint32_t k, uint64_t fixed_m, uint64_t* d_out_offs,
+                                uint32_t flags, hipStream_t st, MmLeafPlan& plan, hipEvent_t* ev) {
+  StreamBuf cnt_leaf, cnt_occ, tmp;
+  FMX_HIP(cnt_leaf.alloc((npat + 1) * 8, st));
+  FMX_HIP(cnt_occ.alloc((npat + 1) * 8, st));
+  FMX_HIP(plan.leaf_base.alloc((npat + 1) * 8, st));
+  const DevIndex ix = query_dev(h, call_flags(h, flags));
+  const unsigned g = grid_for(npat + 1, kBlk, 0xFFFFFFFFu);
+  if (ev) FMX_HIP(hipEventRecord(ev[0], st));
+  with_engine(h->line_fmt, [&](auto engine) {
+    with_int<2, 3, 1>((int)k, [&](auto K) {  // (k = 0 takes K = 1)
+      using E = typename decltype(engine)::type;
+      k_locate_mm<E, K, false><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, k, fixed_m,
+                                                   cnt_leaf.as<uint64_t>(), cnt_occ.as<uint64_t>(),
+                                                   nullptr, nullptr, nullptr, 0, 0);
+    });
+  });
+  FMX_HIP(hipGetLastError());
+  if (ev) FMX_HIP(hipEventRecord(ev[1], st));
+  // the two exclusive scans (one temporary serves both: same type, same length)
+  size_t tb = 0;
+  FMX_HIP(rocprim::exclusive_scan(nullptr, tb, cnt_occ.as<uint64_t>(), d_out_offs, (uint64_t)0,
+                                  npat + 1, rocprim::plus<uint64_t>(), st));
+  FMX_HIP(tmp.alloc(tb, st));
+  FMX_HIP(rocprim::exclusive_scan(tmp.p, tb, cnt_occ.as<uint64_t>(), d_out_offs, (uint64_t)0,
+                                  npat + 1, rocprim::plus<uint64_t>(), st));
+  FMX_HIP(rocprim::exclusive_scan(tmp.p, tb, cnt_leaf.as<uint64_t>(), plan.leaf_base.as<uint64_t>(),
+                                  (uint64_t)0, npat + 1, rocprim::plus<uint64_t>(), st));
+  FMX_HIP(hipMemcpyAsync(&plan.total, d_out_offs + npat, 8, hipMemcpyDeviceToHost, st));
+  FMX_HIP(hipMemcpyAsync(&plan.nleaf, plan.leaf_base.as<uint64_t>() + npat, 8, hipMemcpyDeviceToHost, st));
+  if (ev) FMX_HIP(hipEventRecord(ev[2], st));
+  FMX_HIP(hipStreamSynchronize(st));
+  return CS_OK;
+}
+
+cs_status launch_locate_mm_emit(const cs_fm_index* h, const uint8_t* d_pats, const uint64_t* d_offs,
+                                uint64_t npat, uint32_t k, uint64_t fixed_m,
+                                const uint64_t* d_out_offs, const MmLeafPlan& plan,
+                                uint64_t* d_out_pos, uint8_t* d_out_dist, uint32_t flags,
+                                hipStream_t st, hipEvent_t* ev) {
+  const uint64_t nleaf = plan.nleaf, total = plan.total;
+  StreamBuf leaf_sp, leaf_off, leaf_dist, err;
+  FMX_HIP(leaf_sp.alloc(nleaf * 8, st));
+  FMX_HIP(leaf_off.alloc((nleaf + 1) * 8, st));
+  FMX_HIP(leaf_dist.alloc(nleaf, st));
+  FMX_HIP(err.alloc(8, st));
+  FMX_HIP(hipMemsetAsync(err.p, 0xFF, 8, st));
+  const DevIndex ix = query_dev(h, call_flags(h, flags));
+  const unsigned g = grid_for(npat + 1, kBlk, 0xFFFFFFFFu);
+  with_engine(h->line_fmt, [&](auto engine) {
+    with_int<2, 3, 1>((int)k, [&](auto K) {
+      using E = typename decltype(engine)::type;
+      k_locate_mm<E, K, true><<<g, kBlk, 0, st>>>(
+          ix, d_pats, d_offs, npat, k, fixed_m, plan.leaf_base.as<uint64_t>(),
+          const_cast<uint64_t*>(d_out_offs), leaf_sp.as<uint64_t>(), leaf_off.as<uint64_t>(),
+          leaf_dist.as<uint8_t>(), nleaf, total);
+    });
+  });
+  FMX_HIP(hipGetLastError());
+  if (ev) FMX_HIP(hipEventRecord(ev[3], st));
+  // the positions: the exact locate's phase 2 with the leaves as its patterns
+  unsigned long long* e = err.as<unsigned long long>();
+  cs_status s = launch_locate_walk(h, leaf_sp.as<uint64_t>(), leaf_off.as<uint64_t>(), nleaf, total,
+                                   d_out_pos, st, e, flags);
+  if (s != CS_OK) return s;
+  if (ev) FMX_HIP(hipEventRecord(ev[4], st));
+  if (nleaf) {
+    k_expand_dist<<<grid_for(nleaf, kBlk, 0xFFFFFFFFu), kBlk, 0, st>>>(
+        leaf_off.as<uint64_t>(), leaf_dist.as<uint8_t>(), nleaf, d_out_dist);
+    FMX_HIP(hipGetLastError());
+  }
+  if (ev) FMX_HIP(hipEventRecord(ev[5], st));
+  return check_locate_error(h, e, st);
 }
 
 cs_status launch_count_one(const cs_fm_index* h, const OnePattern& p, uint64_t* out_host,

@@ -1053,6 +1053,102 @@ __device__ __forceinline__ void mm_frame(const DevIndex& ix, const NodeTable& T,
   }
 }
 
+// ---- locate within k mismatches (k_locate_mm; include/cs_fmindex_approx_locate.h) ----
+// Where the search's leaves go: a leaf is a non-empty range [sp, ep) reached at j = 0 with d
+// mismatches spent, the rows of one neighbour.  The sizing pass (leaf_sp == nullptr) only
+// counts; the emitting pass also writes leaf `nleaf` — its first row, its place in the
+// output and its distance — while `nleaf` is below `end`, the pattern's leaf end
+// from the scan of the sizing pass.  One type serves both passes, so both run the same
+// instance of mm_leaves below.
+struct LeafSink {
+  uint64_t nleaf, nocc;  // so far: leaves (sizing: from 0; emitting: from the pattern's first
+                         // leaf) and occurrences (emitting: from the pattern's output offset)
+  uint64_t end;
+  uint64_t* leaf_sp;
+  uint64_t* leaf_off;
+  uint8_t* leaf_dist;
+  __device__ __forceinline__ void leaf(uint32_t d, uint64_t sp, uint64_t ep) {
+    if (leaf_sp && nleaf < end) {
+      leaf_sp[nleaf] = sp;
+      leaf_off[nleaf] = nocc;
+      leaf_dist[nleaf] = (uint8_t)d;
+    }
+    ++nleaf;
+    nocc += ep - sp;
+  }
+};
+
+// mm_frame's traversal with the leaves handed to a sink instead of summed: the same frames,
+// the same order (at each position the substitutes in ascending symbol order, each child
+// exhausted, then the exact path), the same children through E::kids / E::kid.  Frames below
+// kmax branch; frame kmax needs the range itself, not its size, so it takes the remaining
+// characters with plain steps and prunes on the first empty range (count_rest and the prefix
+// table restart return no rows).  kmax is the call's bound k: a frame at depth kmax spends no
+// further mismatch, which is what lets K = 1 serve k = 0.
+// Bounds as in mm_frame: j only decreases (at most m iterations per frame), the symbol cursor
+// i only increases (at most L.n <= 256), the depth is at most K; nothing waits on another lane.
+template <class E>
+__device__ __forceinline__ void mm_rest(const DevIndex& ix, const NodeTable& T, const uint8_t* P,
+                                        uint64_t m, uint32_t d, uint64_t j, uint64_t sp, uint64_t ep,
+                                        LeafSink& sink) {
+  if (j == m) {  // nothing consumed yet: the first range from C[], fm_index.cpp:84-89
+    const uint32_t c = P[j - 1];
+    sp = T.C[c];
+    ep = T.C[c + 1];
+    if (sp == ep) return;
+    --j;
+  }
+  while (j > 0) {  // Bound: j only decreases
+    if (!E::step(ix, T, P[j - 1], sp, ep)) return;
+    --j;
+  }
+  sink.leaf(d, sp, ep);
+}
+template <class E, int D, int K>
+__device__ __forceinline__ void mm_leaves(const DevIndex& ix, const NodeTable& T, const SymList& L,
+                                          const uint8_t* P, uint64_t m, uint32_t kmax, uint64_t j,
+                                          uint64_t sp, uint64_t ep, LeafSink& sink) {
+  if constexpr (D == K) {
+    mm_rest<E>(ix, T, P, m, D, j, sp, ep, sink);
+  } else {
+    if (K == 1 && kmax == 0) {  // (K = 2, 3 are only launched with kmax = K)
+      mm_rest<E>(ix, T, P, m, D, j, sp, ep, sink);
+      return;
+    }
+    while (j > 0) {  // Bound: j only decreases
+      const uint32_t c = P[j - 1];
+      const bool top = D == 0 && j == m;
+      typename E::Kids kd;
+      if (!top) E::kids(ix, T, sp, ep, kd);
+      for (uint32_t i = 0; i < L.n; ++i) {  // Bound: i only increases, L.n <= 256
+        const uint32_t s = L.sym[i];
+        if (s == c) continue;
+        uint64_t csp, cep;
+        bool live = true;
+        if (top) {
+          csp = T.C[s];
+          cep = T.C[s + 1];
+        } else {
+          live = E::kid(ix, T, kd, s, sp, ep, csp, cep);
+        }
+        if (live) mm_leaves<E, D + 1, K>(ix, T, L, P, m, kmax, j - 1, csp, cep, sink);
+      }
+      if (T.C[c] == T.C[c + 1]) return;  // symbol absent: every longer exact path is empty
+      if (top) {
+        sp = T.C[c];
+        ep = T.C[c + 1];
+      } else {
+        uint64_t nsp, nep;
+        if (!E::kid(ix, T, kd, c, sp, ep, nsp, nep)) return;
+        sp = nsp;
+        ep = nep;
+      }
+      --j;
+    }
+    sink.leaf(D, sp, ep);
+  }
+}
+
 // Locate records (phase 1 -> phase 2, cs_fm_locate_ranges_device's d_sp): the
 // first row of the range [sp, ep), or — for a search finished over the left
 // contexts (lf_exact indexes only) — the window of matching rows r at k characters

@@ -4,7 +4,7 @@
 // exceptions as cs::FMIndex (src/api/fm_index.hpp:11-67); the work runs on the GPU
 // through the C ABI in cs_fmindex.h (implementation: csrc/fm_facade.cpp inside
 // libcs_fmindex.so).  Additions: count_batch / locate_batch (one launch for many
-// patterns), count_mismatches (occurrences within k substitutions), save_directory (the on-disk format open_directory reads), handle()
+// patterns), count_mismatches / locate_mismatches (occurrences within k substitutions and their positions), save_directory (the on-disk format open_directory reads), handle()
 // for the raw ABI, borrow() to wrap an ABI handle and serve() (resident
 // single-pattern server).  Errors are
 // std::runtime_error with the reference's message text ("locate: LF walk exceeded
@@ -19,6 +19,7 @@
 #include <memory>
 #include <string>
 #include <string_view>
+#include <utility>
 #include <vector>
 
 struct cs_fm_index;
@@ -56,6 +57,11 @@ class FMIndex {
   // values, [d] = the summed counts of the strings at Hamming distance d from the pattern.
   // Throws std::invalid_argument for k > 3.
   std::vector<uint64_t> count_mismatches(std::string_view pattern, unsigned k) const;
+  // The positions behind those counts (cs_fmindex_approx_locate.h): every (position, distance)
+  // with distance <= k, in the search's order (one neighbour's positions contiguous, in row
+  // order).  An empty pattern has none, as locate().  Throws as count_mismatches does.
+  std::vector<std::pair<uint64_t, uint8_t>> locate_mismatches(std::string_view pattern,
+                                                              unsigned k) const;
 
   // Serving mode for single-pattern count(): a resident wave answers from a pinned
   // mailbox instead of one kernel launch per call (cs_fm_serve_start / _stop).
