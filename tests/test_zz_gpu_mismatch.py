@@ -8,18 +8,15 @@ The file's 62 tests take 4.3 s on one MI355X (the C++ program's wrapper 0.7 s mo
 The file is named to collect after every suite that was here before it, so those keep the
 positions they had in a run.
 """
-import itertools
-
 import numpy as np
 import pytest
 import torch
 
 import oracle as O
 from conftest import load_pkg
+from helpers.mismatch_ref import KMAX, _absent_byte, _dev, _present, device_hist, expected_hist
 
 pytestmark = pytest.mark.gpu
-
-KMAX = 3
 
 # one variant per instantiation of with_engine (fm_search.hpp): occurrence lines with and
 # without the prefix table, learned lines, the quaternary matrix, the binary wavelet matrix in
@@ -59,15 +56,6 @@ TEXTS = {
 }
 
 
-def _present(text):
-    return sorted(set(text))
-
-
-def _absent_byte(text):
-    have = set(text)
-    return next(b for b in b"#%&0123456789" if b not in have)
-
-
 def _patterns(name, text):
     """Substrings of length 1, 2, 3, 8 at random positions; the same with one and two
     characters replaced by other present symbols; a byte absent from the text at the first, a
@@ -100,41 +88,6 @@ def _patterns(name, text):
     return pats
 
 
-def _neighbours(p, syms, d):
-    """Every string at Hamming distance d from p over syms, as a uint8 [count, len(p)] array."""
-    a = np.frombuffer(p, np.uint8)
-    m = len(a)
-    out = [np.zeros((0, m), np.uint8)]
-    if d <= m:
-        for pos in itertools.combinations(range(m), d):
-            subs = [[s for s in syms if s != a[i]] for i in pos]
-            tuples = list(itertools.product(*subs))
-            prod = np.array(tuples, np.uint8).reshape(len(tuples), d)
-            blk = np.tile(a, (len(prod), 1))
-            blk[:, list(pos)] = prod
-            out.append(blk)
-    return np.concatenate(out)
-
-
-def expected_hist(ref, text, pats, k):
-    """uint64 [len(pats), k + 1]: the oracle sum of the definition."""
-    syms = _present(text)
-    chunks, lens, gid = [], [], []
-    for q, p in enumerate(pats):
-        for d in range(k + 1):
-            nb = _neighbours(p, syms, d)
-            chunks.append(nb.reshape(-1))
-            lens.append(np.full(len(nb), len(p), np.uint64))
-            gid.append(np.full(len(nb), q * (k + 1) + d, np.int64))
-    lens = np.concatenate(lens)
-    offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
-    buf = np.concatenate(chunks + [np.zeros(1, np.uint8)])
-    cnt = ref.count_batch(buf=buf, offs=offs, nthreads=8)
-    tot = np.bincount(np.concatenate(gid), weights=cnt.astype(np.float64), minlength=len(pats) * (k + 1))
-    assert tot.max(initial=0) < 2.0 ** 53
-    return tot.astype(np.uint64).reshape(len(pats), k + 1)
-
-
 _CASES = {}
 
 
@@ -146,31 +99,6 @@ def _case(name):
         pats = _patterns(name, text)
         _CASES[name] = (text, pats, expected_hist(ref, text, pats, KMAX), ref)
     return _CASES[name]
-
-
-def _dev(a, dtype):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).cuda()
-
-
-def device_hist(g, pats, k, flags=0, fixed_m=None, canary_rows=1):
-    """count_mismatch_device over CSR offsets (or fixed_m with d_offs = NULL) -> [npat, k + 1];
-    the rows after the last histogram row must come back untouched."""
-    pkg = load_pkg()
-    st = torch.cuda.current_stream().cuda_stream
-    buf, offs = pkg.pack_patterns(pats)
-    npat = len(pats)
-    d_p = _dev(buf, torch.uint8)
-    d_o = _dev(offs.astype(np.int64), torch.int64)
-    d_h = torch.full(((npat + canary_rows) * (k + 1),), -1, dtype=torch.int64, device="cuda")
-    if fixed_m is None:
-        g.count_mismatch_device(d_p.data_ptr(), d_o.data_ptr(), npat, k, d_h.data_ptr(), flags=flags, stream=st)
-    else:
-        g.count_mismatch_device(d_p.data_ptr(), None, npat, k, d_h.data_ptr(), fixed_m=fixed_m, flags=flags,
-                                stream=st)
-    torch.cuda.synchronize()
-    h = d_h.cpu().numpy().view(np.uint64).reshape(npat + canary_rows, k + 1)
-    assert (h[npat:] == np.uint64(0xFFFFFFFFFFFFFFFF)).all(), "canary row overwritten"
-    return h[:npat]
 
 
 # ---- 1. engines x small texts -------------------------------------------------

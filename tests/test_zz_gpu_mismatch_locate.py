@@ -13,19 +13,16 @@ exceeded text length" on both (no unique terminator), so abab_noterm is the over
 The file's 48 tests take 13 s on one MI355X, 0.3-0.6 s per case (the C++ program's wrapper 0.7 s
 more).  The file is named to collect after every suite that was here before it.
 """
-import itertools
-
 import numpy as np
 import pytest
 import torch
 
 import oracle as O
 from conftest import load_pkg
+from helpers.mismatch_ref import (KMAX, _absent_byte, _check, _cut, _dev, _present, device_pairs, expected_pairs,
+                                  host_pairs)
 
 pytestmark = pytest.mark.gpu
-
-KMAX = 3
-CANARY = 16  # entries after the last one, prefilled with all-ones bytes
 
 VARIANTS = {
     "auto": {},
@@ -60,15 +57,6 @@ TEXTS = {
 }
 
 
-def _present(text):
-    return sorted(set(text))
-
-
-def _absent_byte(text):
-    have = set(text)
-    return next(b for b in b"#%&0123456789" if b not in have)
-
-
 def _patterns(name, text):
     """Substrings of length 1, 2, 3, 8 at random positions; the same with one and two
     characters replaced by other present symbols; a byte absent from the text at the first, a
@@ -101,56 +89,6 @@ def _patterns(name, text):
     return pats
 
 
-def _neighbours(p, syms, d):
-    """Every string at Hamming distance d from p over syms, as a uint8 [count, len(p)] array."""
-    a = np.frombuffer(p, np.uint8)
-    m = len(a)
-    out = [np.zeros((0, m), np.uint8)]
-    if d <= m:
-        for pos in itertools.combinations(range(m), d):
-            subs = [[s for s in syms if s != a[i]] for i in pos]
-            tuples = list(itertools.product(*subs))
-            prod = np.array(tuples, np.uint8).reshape(len(tuples), d)
-            blk = np.tile(a, (len(prod), 1))
-            blk[:, list(pos)] = prod
-            out.append(blk)
-    return np.concatenate(out)
-
-
-def expected_pairs(ref, text, pats, k, syms=None):
-    """Per pattern the sorted (pos, d) pairs of the definition, as an int64 [count, 2] array,
-    and the largest number of rows one neighbour (one leaf of the search) holds."""
-    syms = _present(text) if syms is None else syms
-    n = len(text)
-    chunks, lens, owner, dist = [], [], [], []
-    for q, p in enumerate(pats):
-        if not p:
-            continue  # fm_index.cpp:109: an empty pattern has no positions
-        for d in range(k + 1):
-            nb = _neighbours(p, syms, d)
-            chunks.append(nb.reshape(-1))
-            lens.append(np.full(len(nb), len(p), np.uint64))
-            owner.append(np.full(len(nb), q, np.int64))
-            dist.append(np.full(len(nb), d, np.int64))
-    lens, owner, dist = np.concatenate(lens), np.concatenate(owner), np.concatenate(dist)
-    offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
-    buf = np.concatenate(chunks + [np.zeros(1, np.uint8)])
-    cnt = ref.count_batch(buf=buf, offs=offs, nthreads=8)
-    hit = np.flatnonzero(cnt)
-    hbuf = np.concatenate([buf[int(offs[i]):int(offs[i + 1])] for i in hit] + [np.zeros(1, np.uint8)])
-    hoffs = np.concatenate([[0], np.cumsum(lens[hit])]).astype(np.uint64)
-    loffs, lpos = ref.locate_batch(buf=hbuf, offs=hoffs, limit=n + 1, nthreads=8)
-    per = np.diff(loffs.astype(np.int64))
-    assert per.tolist() == cnt[hit].astype(np.int64).tolist()
-    own, dd = np.repeat(owner[hit], per), np.repeat(dist[hit], per)
-    out = []
-    for q in range(len(pats)):
-        sel = own == q
-        pairs = np.stack([lpos[sel].astype(np.int64), dd[sel]], axis=1).reshape(-1, 2)
-        out.append(pairs[np.lexsort((pairs[:, 1], pairs[:, 0]))])
-    return out, int(per.max(initial=0))
-
-
 _CASES = {}
 
 
@@ -163,72 +101,6 @@ def _case(name):
         want, widest = expected_pairs(ref, text, pats, KMAX)
         _CASES[name] = (text, pats, want, widest, ref)
     return _CASES[name]
-
-
-def _cut(want, k):
-    return [w[w[:, 1] <= k] for w in want]
-
-
-def _dev(a, dtype):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).cuda()
-
-
-def device_pairs(g, pats, k, flags=0, fixed_m=None, raw=False):
-    """locate_mismatch_device (a sizing call with cap = 0 and null outputs, then the call) over
-    CSR offsets, or fixed_m with d_offs = NULL -> (offsets, per-pattern sorted pairs); the
-    entries after the last position and distance must come back untouched.  raw: the
-    positions and distances as written."""
-    pkg = load_pkg()
-    st = torch.cuda.current_stream().cuda_stream
-    buf, offs = pkg.pack_patterns(pats)
-    npat = len(pats)
-    d_p = _dev(buf if len(buf) else np.zeros(1, np.uint8), torch.uint8)
-    d_o = _dev(offs.astype(np.int64), torch.int64)
-    kw = dict(flags=flags, stream=st)
-    if fixed_m is not None:
-        kw["fixed_m"] = fixed_m
-    d_offs_arg = d_o.data_ptr() if fixed_m is None else None
-    d_oo = torch.full((npat + 1,), -1, dtype=torch.int64, device="cuda")
-    total, written = g.locate_mismatch_device(d_p.data_ptr(), d_offs_arg, npat, k, d_oo.data_ptr(), None, None, 0,
-                                              **kw)
-    assert written == (total == 0)
-    sized = d_oo.cpu().numpy().copy()
-    d_pos = torch.full((total + CANARY,), -1, dtype=torch.int64, device="cuda")
-    d_dist = torch.full((total + CANARY,), 0xFF, dtype=torch.uint8, device="cuda")
-    d_oo.fill_(-1)
-    tot2, written = g.locate_mismatch_device(d_p.data_ptr(), d_offs_arg, npat, k, d_oo.data_ptr(),
-                                             d_pos.data_ptr(), d_dist.data_ptr(), total, **kw)
-    torch.cuda.synchronize()
-    assert written and tot2 == total
-    oo = d_oo.cpu().numpy()
-    assert oo.tolist() == sized.tolist() and oo[-1] == total
-    pos, dist = d_pos.cpu().numpy(), d_dist.cpu().numpy()
-    assert (pos[total:] == -1).all() and (dist[total:] == 0xFF).all(), "canary overwritten"
-    if raw:
-        return oo, pos[:total], dist[:total]
-    return oo, _split(oo, pos[:total], dist[:total])
-
-
-def _split(oo, pos, dist):
-    out = []
-    for q in range(len(oo) - 1):
-        a, b = int(oo[q]), int(oo[q + 1])
-        pairs = np.stack([pos[a:b].astype(np.int64), dist[a:b].astype(np.int64)], axis=1).reshape(-1, 2)
-        out.append(pairs[np.lexsort((pairs[:, 1], pairs[:, 0]))])
-    return out
-
-
-def _check(got_offs, got, want, what):
-    sizes = [len(w) for w in want]
-    assert np.asarray(got_offs).astype(np.int64).tolist() == np.concatenate([[0], np.cumsum(sizes)]).tolist(), what
-    for q, (a, b) in enumerate(zip(got, want)):
-        assert a.tolist() == b.tolist(), (what, q)
-
-
-def host_pairs(g, pats, k):
-    oo, pos, dist = g.locate_mismatches_batch(pats, k)
-    assert pos.dtype == np.uint64 and dist.dtype == np.uint8 and len(pos) == len(dist) == oo[-1]
-    return oo, _split(oo, pos, dist)
 
 
 # ---- 1. engines x small texts -------------------------------------------------
