@@ -40,6 +40,8 @@ QT_WALK_ROWS, QT_WALK_PERSISTENT, QT_GENERAL_INLANE, QT_GENERAL_LIST_ALL = 1 << 
 QT_MAP_LDS = 1 << 24
 # the largest mismatch bound of count_mismatches (include/cs_fmindex_approx.h CS_MM_MAX)
 CS_MM_MAX = 3
+# best_dist of a pattern with no occurrence within k (include/cs_fmindex_approx_best.h CS_MM_NONE)
+CS_MM_NONE = 0xFF
 
 _u8p = C.POINTER(C.c_uint8)
 _u64p = C.POINTER(C.c_uint64)
@@ -113,7 +115,7 @@ class cs_fm_info(C.Structure):
 
 
 # Every entry point of include/cs_fmindex.h (and cs_fmindex_diag.h, cs_fmindex_replica.h,
-# cs_fmindex_approx.h, cs_fmindex_approx_locate.h, cs_synth.h)
+# cs_fmindex_approx.h, cs_fmindex_approx_locate.h, cs_fmindex_approx_best.h, cs_synth.h)
 # with its ctypes signature.
 SIGNATURES = {
     "cs_default_build_params": (None, [C.POINTER(cs_build_params)]),
@@ -205,6 +207,11 @@ SIGNATURES = {
                                               _u8p, C.c_uint64, _u64p, _vp]),
     "cs_fm_locate_mismatch": (C.c_int, [_vp, C.c_char_p, C.c_uint64, C.c_uint32, _u64p, _u8p,
                                         C.c_uint64, _u64p]),
+    # include/cs_fmindex_approx_best.h (the smallest distance with a hit, and its count)
+    "cs_fm_best_mismatch_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_uint32, _vp, _vp,
+                                             C.c_uint32, _vp]),
+    "cs_fm_best_mismatch_batch": (C.c_int, [_vp, _u8p, _u64p, C.c_uint64, C.c_uint32, _u8p, _u64p, _vp]),
+    "cs_fm_best_mismatch": (C.c_int, [_vp, C.c_char_p, C.c_uint64, C.c_uint32, _u8p, _u64p]),
 }
 
 _lib = None
@@ -510,6 +517,40 @@ class FMIndex:
         fixed_m back to back; flags Q_* leave structures out (same results)."""
         _check(lib().cs_fm_count_mismatch_device(self._h, d_pats or None, d_offs or None, fixed_m, npat, k,
                                                  d_hist, flags, stream or None))
+
+    # -- best stratum within k mismatches (include/cs_fmindex_approx_best.h) ----
+    def best_mismatch(self, pattern, k: int):
+        """-> (dist, count): the smallest Hamming distance dist <= k at which `pattern` occurs
+        and the count at that distance (cs_fm_best_mismatch); (None, 0) when there is none
+        within k.  k <= CS_MM_MAX."""
+        b = _bytes(pattern)
+        dist = np.full(1, CS_MM_NONE, np.uint8)
+        cnt = np.zeros(1, np.uint64)
+        _check(lib().cs_fm_best_mismatch(self._h, b, len(b), k, _u8(dist), _u64(cnt)))
+        return (None if dist[0] == CS_MM_NONE else int(dist[0])), int(cnt[0])
+
+    def best_mismatches_batch(self, patterns=None, k: int = 1, buf=None, offs=None):
+        """-> (dist uint8[npat], count uint64[npat]): per pattern the smallest distance <= k with
+        a hit (CS_MM_NONE when none) and its count (cs_fm_best_mismatch_batch)."""
+        if patterns is not None:
+            buf, offs = pack_patterns(patterns)
+        buf = np.ascontiguousarray(buf, np.uint8)
+        if len(buf) == 0:
+            buf = np.zeros(1, np.uint8)
+        offs = np.ascontiguousarray(offs, np.uint64)
+        npat = len(offs) - 1
+        dist = np.full(max(npat, 1), CS_MM_NONE, np.uint8)
+        cnt = np.zeros(max(npat, 1), np.uint64)
+        _check(lib().cs_fm_best_mismatch_batch(self._h, _u8(buf), _u64(offs), npat, k, _u8(dist), _u64(cnt),
+                                               None))
+        return dist[:npat], cnt[:npat]
+
+    def best_mismatch_device(self, d_pats, d_offs, npat, k, d_dist, d_count, fixed_m=0, flags=0, stream=None):
+        """Best strata of a device batch into d_dist (uint8 [npat]) and d_count (uint64 [npat]),
+        asynchronous on `stream` (cs_fm_best_mismatch_device): d_offs or None for npat patterns
+        of length fixed_m back to back; flags Q_* leave structures out (same results)."""
+        _check(lib().cs_fm_best_mismatch_device(self._h, d_pats or None, d_offs or None, fixed_m, npat, k,
+                                                d_dist, d_count, flags, stream or None))
 
     # -- positions within k mismatches (include/cs_fmindex_approx_locate.h) ----
     def locate_mismatches(self, pattern, k: int):

@@ -1116,6 +1116,61 @@ cs_status cs_fm_count_mismatch(const cs_fm_index* h, const uint8_t* pattern, uin
   return cs_fm_count_mismatch_batch(h, pattern, offs, 1, k, out_hist, nullptr);
 }
 
+// ---- best stratum within k mismatches (include/cs_fmindex_approx_best.h) ----
+cs_status cs_fm_best_mismatch_device(const cs_fm_index* h, const uint8_t* d_pats,
+                                     const uint64_t* d_offs, uint64_t fixed_m, uint64_t npat,
+                                     uint32_t k, uint8_t* d_best_dist, uint64_t* d_best_count,
+                                     uint32_t flags, void* stream) {
+  DeviceScope dscope;
+  cs_status s = check_handle(h, dscope);
+  if (s != CS_OK) return s;
+  if ((s = mismatch_bound_ok(k)) != CS_OK) return s;
+  if (npat && (!d_best_dist || !d_best_count || (!d_pats && !d_offs && fixed_m))) {
+    set_error("null batch pointer");
+    return CS_ERR_INVALID;
+  }
+  if ((s = null_pats_ok(d_pats, d_offs, npat, (hipStream_t)stream)) != CS_OK) return s;
+  return launch_best_mm(h, d_pats, d_offs, npat, k, d_best_dist, d_best_count, flags,
+                        (hipStream_t)stream, d_offs ? 0 : fixed_m);
+}
+
+cs_status cs_fm_best_mismatch_batch(const cs_fm_index* h, const uint8_t* pats, const uint64_t* offs,
+                                    uint64_t npat, uint32_t k, uint8_t* out_dist, uint64_t* out_count,
+                                    void* stream) {
+  DeviceScope dscope;
+  cs_status s = check_handle(h, dscope);
+  if (s != CS_OK) return s;
+  if ((s = mismatch_bound_ok(k)) != CS_OK) return s;
+  if (!npat) return CS_OK;
+  if (!offs || !out_dist || !out_count || (!pats && offs[npat] != offs[0])) {
+    set_error("null batch pointer");
+    return CS_ERR_INVALID;
+  }
+  if ((s = check_offsets(offs, npat)) != CS_OK) return s;
+  hipStream_t st = (hipStream_t)stream;
+  HostPin pin_dist, pin_count;
+  StagedBatch b;
+  if ((s = b.load(h, pats, offs, npat, st)) != CS_OK) return s;
+  StreamBuf d_dist, d_count;
+  FMX_HIP(d_dist.alloc(npat, st));
+  FMX_HIP(d_count.alloc(npat * 8, st));
+  pin_dist.pin(h, out_dist, npat, st);
+  pin_count.pin(h, out_count, npat * 8, st);
+  s = launch_best_mm(h, b.pats.as<uint8_t>(), b.offs.as<uint64_t>(), npat, k, d_dist.as<uint8_t>(),
+                     d_count.as<uint64_t>(), 0, st, 0);
+  if (s != CS_OK) return s;
+  FMX_HIP(pin_dist.copy(out_dist, d_dist.p, npat, false, st));
+  FMX_HIP(pin_count.copy(out_count, d_count.p, npat * 8, false, st));
+  FMX_HIP(hipStreamSynchronize(st));
+  return CS_OK;
+}
+
+cs_status cs_fm_best_mismatch(const cs_fm_index* h, const uint8_t* pattern, uint64_t m, uint32_t k,
+                              uint8_t* out_dist, uint64_t* out_count) {
+  const uint64_t offs[2] = {0, m};
+  return cs_fm_best_mismatch_batch(h, pattern, offs, 1, k, out_dist, out_count, nullptr);
+}
+
 // ---- locate within k mismatches (include/cs_fmindex_approx_locate.h) ----
 // the device batch; phase_ms: null, or the five phase times of cs_fm_locate_mismatch_phases_device
 static cs_status locate_mismatch_device(const cs_fm_index* h, const uint8_t* d_pats,

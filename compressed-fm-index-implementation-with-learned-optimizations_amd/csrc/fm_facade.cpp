@@ -8,6 +8,7 @@
 
 #include "../../include/cs_fmindex.h"
 #include "../../include/cs_fmindex_approx.h"
+#include "../../include/cs_fmindex_approx_best.h"
 #include "../../include/cs_fmindex_approx_locate.h"
 
 namespace cs {
@@ -151,6 +152,20 @@ std::vector<uint64_t> FMIndex::count_mismatches(std::string_view pattern, unsign
                                      pattern.size(), k, hist.data());
   if (s != CS_OK) raise(s);
   return hist;
+}
+
+std::pair<int, uint64_t> FMIndex::best_mismatch(std::string_view pattern, unsigned k) const {
+  if (k > CS_MM_MAX) throw std::invalid_argument("best_mismatch: k must be at most 3");
+  if (!h_) {  // an empty index, as count()
+    if (pattern.empty() && meta_.n) return {0, meta_.n};
+    return {-1, 0};
+  }
+  uint8_t d = CS_MM_NONE;
+  uint64_t c = 0;
+  cs_status s = cs_fm_best_mismatch(h_.get(), reinterpret_cast<const uint8_t*>(pattern.data()),
+                                    pattern.size(), k, &d, &c);
+  if (s != CS_OK) raise(s);
+  return {d == CS_MM_NONE ? -1 : (int)d, c};
 }
 
 std::vector<std::pair<uint64_t, uint8_t>> FMIndex::locate_mismatches(std::string_view pattern,

@@ -15,6 +15,7 @@
 #include "../../include/cs_fmindex_replica.h"
 #include "../../include/cs_fmindex_approx.h"
 #include "../../include/cs_fmindex_approx_locate.h"
+#include "../../include/cs_fmindex_approx_best.h"
 #include "fm_device.hpp"
 
 struct cs_fm_index {
@@ -287,6 +288,12 @@ cs_status launch_count_ex(const cs_fm_index* h, const uint8_t* d_pats, const uin
 cs_status launch_count_mm(const cs_fm_index* h, const uint8_t* d_pats, const uint64_t* d_offs,
                           uint64_t npat, uint32_t k, uint64_t* d_hist, uint32_t flags, hipStream_t st,
                           uint64_t fixed_m);
+// best stratum within k <= CS_MM_MAX mismatches (cs_fmindex_approx_best.h): rounds 0..k back to
+// back on st, d_best_dist[npat] and d_best_count[npat]; its lists are stream-ordered
+// temporaries and it never synchronises
+cs_status launch_best_mm(const cs_fm_index* h, const uint8_t* d_pats, const uint64_t* d_offs,
+                         uint64_t npat, uint32_t k, uint8_t* d_best_dist, uint64_t* d_best_count,
+                         uint32_t flags, hipStream_t st, uint64_t fixed_m);
 cs_status launch_count_one(const cs_fm_index* h, const fmx::OnePattern& p, uint64_t* out_host,
                            hipStream_t st);
 cs_status launch_count_bytes(const cs_fm_index* h, const uint8_t* d_pats, const uint64_t* d_offs,

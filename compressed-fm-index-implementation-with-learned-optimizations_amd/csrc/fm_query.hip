@@ -95,6 +95,77 @@ __global__ __launch_bounds__(kBlk) void k_count_mm(DevIndex ix, const uint8_t* _
     if ((uint32_t)d <= k) out[d] = h[d];
 }
 
+// Best stratum (cs_fm_best_mismatch_device): round K of launch_best_mm, one pattern per lane.
+// Round 0 runs over every pattern (the exact count, empty patterns and n = 0 as in
+// k_count_mm); round K >= 1 over a pending list, list_in[0 .. *len_in): the patterns with no
+// hit at any distance below K, so mm_frame<E, 0, K>'s columns below K are zero and only h[K]
+// is taken.  A lane whose count is not zero writes (K, count); one without a hit appends its
+// pattern to list_out — one ballot and one atomicAdd on *len_out per wave, the lanes scatter
+// by their prefix popcount — or, in the last round, writes (CS_MM_NONE, 0).  So every
+// pattern's outputs are written exactly once over the rounds.  The grid is sized for npat (the
+// host never reads a length): a block whose first entry is at or past the list's length
+// returns before it stages anything, a block-uniform test ahead of every barrier.  Nothing
+// waits on another wave or block, and every loop is bounded as mm_frame's are.  list_out
+// holds npat entries and receives at most *len_in <= npat.
+template <class E, int K>
+__global__ __launch_bounds__(kBlk) void k_best_mm(DevIndex ix, const uint8_t* __restrict__ pats,
+                                                  const uint64_t* __restrict__ offs, uint64_t npat,
+                                                  uint64_t fixed_m, bool last,
+                                                  const uint64_t* __restrict__ list_in,
+                                                  const unsigned long long* __restrict__ len_in,
+                                                  uint64_t* __restrict__ list_out,
+                                                  unsigned long long* len_out,
+                                                  uint8_t* __restrict__ best_dist,
+                                                  uint64_t* __restrict__ best_count) {
+  uint64_t nlist = npat;
+  if constexpr (K > 0) {
+    nlist = *len_in;
+    if (blockIdx.x * (uint64_t)blockDim.x >= nlist) return;
+  }
+  __shared__ NodeTable T;
+  __shared__ SymList L;
+  load_table(T, ix.table);
+  __syncthreads();
+  if constexpr (K > 0) list_symbols(L, T);
+  const uint64_t e = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  // (no early return for the lanes past the list: the append below is per wave)
+  uint64_t q = 0;
+  bool miss = false;
+  if (e < nlist) {
+    if constexpr (K > 0) q = list_in[e];
+    else q = e;
+    const uint64_t o0 = offs ? offs[q] : q * fixed_m, m = offs ? offs[q + 1] - o0 : fixed_m;
+    uint64_t cnt = 0;
+    if constexpr (K == 0) {
+      if (m == 0) cnt = ix.n;  // fm_index.cpp:80
+      else if (ix.n != 0) cnt = count_pattern<E>(ix, T, pats + o0, m);  // :81
+    } else if (m != 0 && ix.n != 0) {
+      uint64_t h[K + 1];
+#pragma unroll
+      for (int d = 0; d <= K; ++d) h[d] = 0;
+      SubPat<K> S;
+      S.b = pats + o0;
+#pragma unroll
+      for (int t = 0; t < K; ++t) S.pos[t] = ~0ull, S.sym[t] = 0;
+      mm_frame<E, 0, K>(ix, T, L, S, m, m, 0, ix.n, h);
+      cnt = h[K];
+    }
+    miss = cnt == 0 && !last;
+    if (!miss) {
+      best_dist[q] = cnt ? (uint8_t)K : (uint8_t)CS_MM_NONE;
+      best_count[q] = cnt;
+    }
+  }
+  const uint64_t bal = __ballot(miss);
+  if (bal) {  // wave-uniform
+    const uint32_t lane = threadIdx.x & 63, lead = (uint32_t)__ffsll((unsigned long long)bal) - 1u;
+    unsigned long long base = 0;
+    if (lane == lead) base = atomicAdd(len_out, (unsigned long long)__popcll(bal));
+    base = __shfl(base, (int)lead);
+    if (miss) list_out[base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = q;
+  }
+}
+
 // Locate within k <= K mismatches (cs_fm_locate_mismatch_device): one pattern per lane, the
 // traversal of mm_leaves (fm_search.hpp; k_count_mm's search with a leaf sink), run twice.
 // Sizing (kEmit = false): cnt_leaf[q] / cnt_occ[q] = the pattern's non-empty leaf ranges and
@@ -4124,6 +4195,38 @@ cs_status launch_count_mm(const cs_fm_index* h, const uint8_t* d_pats, const uin
       using E = typename decltype(engine)::type;
       k_count_mm<E, K><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, k, d_hist, fixed_m);
     });
+  });
+  FMX_HIP(hipGetLastError());
+  return CS_OK;
+}
+
+cs_status launch_best_mm(const cs_fm_index* h, const uint8_t* d_pats, const uint64_t* d_offs,
+                         uint64_t npat, uint32_t k, uint8_t* d_best_dist, uint64_t* d_best_count,
+                         uint32_t flags, hipStream_t st, uint64_t fixed_m) {
+  if (!npat) return CS_OK;
+  // round r reads list r - 1 and appends to list r; the lists alternate between the two
+  // halves of `lists`, len[r] is list r's length
+  StreamBuf lists, len;
+  if (k) {
+    FMX_HIP(lists.alloc(2 * npat * 8, st));
+    FMX_HIP(len.alloc(CS_MM_MAX * 8, st));
+    FMX_HIP(hipMemsetAsync(len.p, 0, CS_MM_MAX * 8, st));
+  }
+  const DevIndex ix = query_dev(h, call_flags(h, flags));
+  // a round's list length is known on the device only: every round's grid covers npat
+  const unsigned g = grid_for(npat, kBlk, 0xFFFFFFFFu);
+  with_engine(h->line_fmt, [&](auto engine) {
+    using E = typename decltype(engine)::type;
+    for (uint32_t r = 0; r <= k; ++r) {
+      uint64_t* const in = r ? lists.as<uint64_t>() + ((r - 1) & 1) * npat : nullptr;
+      uint64_t* const out = r < k ? lists.as<uint64_t>() + (r & 1) * npat : nullptr;
+      unsigned long long* const ln = len.as<unsigned long long>();
+      with_int<0, 1, 2, 3>((int)r, [&](auto K) {
+        k_best_mm<E, K><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, fixed_m, /*last*/ r == k, in,
+                                            r ? ln + (r - 1) : nullptr, out, r < k ? ln + r : nullptr,
+                                            d_best_dist, d_best_count);
+      });
+    }
   });
   FMX_HIP(hipGetLastError());
   return CS_OK;

@@ -4,7 +4,7 @@
 // exceptions as cs::FMIndex (src/api/fm_index.hpp:11-67); the work runs on the GPU
 // through the C ABI in cs_fmindex.h (implementation: csrc/fm_facade.cpp inside
 // libcs_fmindex.so).  Additions: count_batch / locate_batch (one launch for many
-// patterns), count_mismatches / locate_mismatches (occurrences within k substitutions and their positions), save_directory (the on-disk format open_directory reads), handle()
+// patterns), count_mismatches / locate_mismatches / best_mismatch (occurrences within k substitutions, their positions, and the smallest distance with a hit), save_directory (the on-disk format open_directory reads), handle()
 // for the raw ABI, borrow() to wrap an ABI handle and serve() (resident
 // single-pattern server).  Errors are
 // std::runtime_error with the reference's message text ("locate: LF walk exceeded
@@ -57,6 +57,10 @@ class FMIndex {
   // values, [d] = the summed counts of the strings at Hamming distance d from the pattern.
   // Throws std::invalid_argument for k > 3.
   std::vector<uint64_t> count_mismatches(std::string_view pattern, unsigned k) const;
+  // The best stratum (cs_fmindex_approx_best.h): the smallest distance d <= k at which the
+  // pattern occurs and the count at that distance, (-1, 0) when there is none within k.
+  // Throws as count_mismatches does.
+  std::pair<int, uint64_t> best_mismatch(std::string_view pattern, unsigned k) const;
   // The positions behind those counts (cs_fmindex_approx_locate.h): every (position, distance)
   // with distance <= k, in the search's order (one neighbour's positions contiguous, in row
   // order).  An empty pattern has none, as locate().  Throws as count_mismatches does.
