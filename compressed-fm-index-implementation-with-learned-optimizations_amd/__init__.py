@@ -115,7 +115,8 @@ class cs_fm_info(C.Structure):
 
 
 # Every entry point of include/cs_fmindex.h (and cs_fmindex_diag.h, cs_fmindex_replica.h,
-# cs_fmindex_approx.h, cs_fmindex_approx_locate.h, cs_fmindex_approx_best.h, cs_synth.h)
+# cs_fmindex_approx.h, cs_fmindex_approx_locate.h, cs_fmindex_approx_best.h,
+# cs_fmindex_approx_best_locate.h, cs_synth.h)
 # with its ctypes signature.
 SIGNATURES = {
     "cs_default_build_params": (None, [C.POINTER(cs_build_params)]),
@@ -212,6 +213,13 @@ SIGNATURES = {
                                              C.c_uint32, _vp]),
     "cs_fm_best_mismatch_batch": (C.c_int, [_vp, _u8p, _u64p, C.c_uint64, C.c_uint32, _u8p, _u64p, _vp]),
     "cs_fm_best_mismatch": (C.c_int, [_vp, C.c_char_p, C.c_uint64, C.c_uint32, _u8p, _u64p]),
+    # include/cs_fmindex_approx_best_locate.h (the positions at that smallest distance only)
+    "cs_fm_locate_best_mismatch_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_uint32, _vp,
+                                                    _vp, _vp, C.c_uint64, _u64p, C.c_uint32, _vp]),
+    "cs_fm_locate_best_mismatch_batch": (C.c_int, [_vp, _u8p, _u64p, C.c_uint64, C.c_uint32, _u8p, _u64p,
+                                                   _u64p, C.c_uint64, _u64p, _vp]),
+    "cs_fm_locate_best_mismatch": (C.c_int, [_vp, C.c_char_p, C.c_uint64, C.c_uint32, _u8p, _u64p,
+                                             C.c_uint64, _u64p]),
 }
 
 _lib = None
@@ -551,6 +559,57 @@ class FMIndex:
         of length fixed_m back to back; flags Q_* leave structures out (same results)."""
         _check(lib().cs_fm_best_mismatch_device(self._h, d_pats or None, d_offs or None, fixed_m, npat, k,
                                                 d_dist, d_count, flags, stream or None))
+
+    # -- best-stratum locate (include/cs_fmindex_approx_best_locate.h) ----
+    def locate_best_mismatches(self, pattern, k: int):
+        """-> (dist, pos uint64[]): the smallest Hamming distance dist <= k at which `pattern`
+        occurs (None when there is none within k) and the positions at that distance only, in
+        the search's order (cs_fm_locate_best_mismatch).  k <= CS_MM_MAX."""
+        dist, _, pos = self.locate_best_mismatches_batch([_bytes(pattern)], k)
+        return (None if dist[0] == CS_MM_NONE else int(dist[0])), pos
+
+    def locate_best_mismatches_batch(self, patterns=None, k: int = 1, buf=None, offs=None):
+        """-> (dist uint8[npat], out_offs uint64[npat + 1], pos uint64[]): per pattern the
+        smallest distance <= k with a hit (CS_MM_NONE when none) and its positions at that
+        distance at [out_offs[q], out_offs[q + 1]) (cs_fm_locate_best_mismatch_batch; a first
+        call sizes the output)."""
+        if patterns is not None:
+            buf, offs = pack_patterns(patterns)
+        buf = np.ascontiguousarray(buf, np.uint8)
+        if len(buf) == 0:
+            buf = np.zeros(1, np.uint8)
+        offs = np.ascontiguousarray(offs, np.uint64)
+        npat = len(offs) - 1
+        dist = np.full(max(npat, 1), CS_MM_NONE, np.uint8)
+        out_offs = np.zeros(npat + 1, np.uint64)
+        total = C.c_uint64()
+        st = lib().cs_fm_locate_best_mismatch_batch(self._h, _u8(buf), _u64(offs), npat, k, _u8(dist),
+                                                    _u64(out_offs), None, 0, C.byref(total), None)
+        if st == CS_OK:
+            return dist[:npat], out_offs, np.zeros(0, np.uint64)
+        if st != CS_ERR_CAPACITY:
+            _check(st)
+        pos = np.zeros(total.value, np.uint64)
+        _check(lib().cs_fm_locate_best_mismatch_batch(self._h, _u8(buf), _u64(offs), npat, k, _u8(dist),
+                                                      _u64(out_offs), _u64(pos), total.value,
+                                                      C.byref(total), None))
+        return dist[:npat], out_offs, pos
+
+    def locate_best_mismatch_device(self, d_pats, d_offs, npat, k, d_dist, d_out_offs, d_out_pos, cap,
+                                    fixed_m=0, flags=0, stream=0):
+        """Best strata and their positions of a device batch (cs_fm_locate_best_mismatch_device):
+        distances into d_dist (uint8 [npat]), offsets into d_out_offs[npat + 1] and, when the
+        total fits `cap`, positions into d_out_pos -> (total, written).  d_offs or None for npat
+        patterns of length fixed_m back to back; cap = 0 with a null d_out_pos sizes; flags Q_*
+        leave structures out (same results)."""
+        total = C.c_uint64()
+        st = lib().cs_fm_locate_best_mismatch_device(self._h, d_pats or None, d_offs or None, fixed_m, npat,
+                                                     k, d_dist or None, d_out_offs, d_out_pos or None, cap,
+                                                     C.byref(total), flags, stream or None)
+        if st == CS_ERR_CAPACITY:
+            return total.value, False
+        _check(st)
+        return total.value, True
 
     # -- positions within k mismatches (include/cs_fmindex_approx_locate.h) ----
     def locate_mismatches(self, pattern, k: int):

@@ -1324,6 +1324,120 @@ cs_status cs_fm_locate_mismatch(const cs_fm_index* h, const uint8_t* pattern, ui
   return s;
 }
 
+// ---- best-stratum locate (include/cs_fmindex_approx_best_locate.h) ----
+cs_status cs_fm_locate_best_mismatch_device(const cs_fm_index* h, const uint8_t* d_pats,
+                                            const uint64_t* d_offs, uint64_t fixed_m, uint64_t npat,
+                                            uint32_t k, uint8_t* d_best_dist, uint64_t* d_out_offs,
+                                            uint64_t* d_out_pos, uint64_t cap, uint64_t* total,
+                                            uint32_t flags, void* stream) {
+  DeviceScope dscope;
+  cs_status s = check_handle(h, dscope);
+  if (s != CS_OK) return s;
+  if ((s = mismatch_bound_ok(k)) != CS_OK) return s;
+  if (!total || !d_out_offs || (cap && !d_out_pos) ||
+      (npat && (!d_best_dist || (!d_pats && !d_offs && fixed_m)))) {
+    set_error("null batch pointer");
+    return CS_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  *total = 0;
+  if (!npat) {
+    FMX_HIP(hipMemsetAsync(d_out_offs, 0, 8, st));
+    FMX_HIP(hipStreamSynchronize(st));
+    return CS_OK;
+  }
+  if ((s = null_pats_ok(d_pats, d_offs, npat, st)) != CS_OK) return s;
+  BestLeafPlan plan;
+  const uint64_t fm = d_offs ? 0 : fixed_m;
+  if ((s = launch_best_locate_mm_size(h, d_pats, d_offs, npat, k, fm, d_best_dist, d_out_offs, flags, st,
+                                      plan)) != CS_OK)
+    return s;
+  *total = plan.total;
+  if (plan.total > cap) {
+    set_error("locate: capacity too small");
+    return CS_ERR_CAPACITY;
+  }
+  if (!plan.total) return CS_OK;
+  return launch_best_locate_mm_emit(h, d_pats, d_offs, npat, k, fm, d_out_offs, plan, d_out_pos, flags, st);
+}
+
+cs_status cs_fm_locate_best_mismatch_batch(const cs_fm_index* h, const uint8_t* pats,
+                                           const uint64_t* offs, uint64_t npat, uint32_t k,
+                                           uint8_t* out_dist, uint64_t* out_offs, uint64_t* out_pos,
+                                           uint64_t cap, uint64_t* total, void* stream) {
+  DeviceScope dscope;
+  cs_status s = check_handle(h, dscope);
+  if (s != CS_OK) return s;
+  if ((s = mismatch_bound_ok(k)) != CS_OK) return s;
+  if (!total || !out_offs) {
+    set_error("null batch pointer");
+    return CS_ERR_INVALID;
+  }
+  *total = 0;
+  if (!npat) {
+    out_offs[0] = 0;
+    return CS_OK;
+  }
+  if (!offs || !out_dist || (!pats && offs[npat] != offs[0])) {
+    set_error("null batch pointer");
+    return CS_ERR_INVALID;
+  }
+  if ((s = check_offsets(offs, npat)) != CS_OK) return s;
+  hipStream_t st = (hipStream_t)stream;
+  StagedBatch b;
+  if ((s = b.load(h, pats, offs, npat, st)) != CS_OK) return s;
+  StreamBuf d_oo, d_dist;
+  FMX_HIP(d_oo.alloc((npat + 1) * 8, st));
+  FMX_HIP(d_dist.alloc(npat, st));
+  BestLeafPlan plan;
+  if ((s = launch_best_locate_mm_size(h, b.pats.as<uint8_t>(), b.offs.as<uint64_t>(), npat, k, 0,
+                                      d_dist.as<uint8_t>(), d_oo.as<uint64_t>(), 0, st, plan)) != CS_OK)
+    return s;
+  *total = plan.total;
+  {
+    HostPin po, pd;
+    po.pin(h, out_offs, (npat + 1) * 8, st);
+    pd.pin(h, out_dist, npat, st);
+    FMX_HIP(po.copy(out_offs, d_oo.p, (npat + 1) * 8, false, st));
+    FMX_HIP(pd.copy(out_dist, d_dist.p, npat, false, st));
+  }
+  FMX_HIP(hipStreamSynchronize(st));
+  if (plan.total > cap) {  // after the sizing step: the position phase does not run
+    set_error("locate output capacity too small");
+    return CS_ERR_CAPACITY;
+  }
+  if (!plan.total) return CS_OK;
+  if (!out_pos) {
+    set_error("null output buffer");
+    return CS_ERR_INVALID;
+  }
+  StreamBuf d_pos;
+  FMX_HIP(d_pos.alloc(plan.total * 8, st));
+  s = launch_best_locate_mm_emit(h, b.pats.as<uint8_t>(), b.offs.as<uint64_t>(), npat, k, 0,
+                                 d_oo.as<uint64_t>(), plan, d_pos.as<uint64_t>(), 0, st);
+  if (s != CS_OK) return s;
+  HostPin pp;
+  pp.pin(h, out_pos, plan.total * 8, st);
+  FMX_HIP(pp.copy(out_pos, d_pos.p, plan.total * 8, false, st));
+  FMX_HIP(hipStreamSynchronize(st));
+  return CS_OK;
+}
+
+cs_status cs_fm_locate_best_mismatch(const cs_fm_index* h, const uint8_t* pattern, uint64_t m, uint32_t k,
+                                     uint8_t* out_dist, uint64_t* out_pos, uint64_t cap, uint64_t* nout) {
+  if (!nout || !out_dist) {
+    set_error(!nout ? "null nout" : "null out_dist");
+    return CS_ERR_INVALID;
+  }
+  const uint64_t offs[2] = {0, m};
+  uint64_t oo[2] = {0, 0};
+  uint64_t total = 0;
+  cs_status s = cs_fm_locate_best_mismatch_batch(h, pattern, offs, 1, k, out_dist, oo, out_pos, cap, &total,
+                                                 nullptr);
+  if (s == CS_OK || s == CS_ERR_CAPACITY) *nout = total;
+  return s;
+}
+
 cs_status cs_fm_locate_check(const cs_fm_index* h, void* stream) {
   DeviceScope dscope;
   cs_status s = check_handle(h, dscope);

@@ -9,6 +9,7 @@
 #include "../../include/cs_fmindex.h"
 #include "../../include/cs_fmindex_approx.h"
 #include "../../include/cs_fmindex_approx_best.h"
+#include "../../include/cs_fmindex_approx_best_locate.h"
 #include "../../include/cs_fmindex_approx_locate.h"
 
 namespace cs {
@@ -184,6 +185,28 @@ std::vector<std::pair<uint64_t, uint8_t>> FMIndex::locate_mismatches(std::string
   if (s != CS_OK) raise(s);
   res.reserve(total);
   for (uint64_t i = 0; i < total; ++i) res.emplace_back(pos[i], dist[i]);
+  return res;
+}
+
+std::pair<int, std::vector<uint64_t>> FMIndex::locate_best_mismatch(std::string_view pattern,
+                                                                    unsigned k) const {
+  if (k > CS_MM_MAX) throw std::invalid_argument("locate_best_mismatch: k must be at most 3");
+  std::pair<int, std::vector<uint64_t>> res{-1, {}};
+  if (!h_) {  // an empty index, as best_mismatch()
+    if (pattern.empty() && meta_.n) res.first = 0;
+    return res;
+  }
+  const uint8_t* p = reinterpret_cast<const uint8_t*>(pattern.data());
+  uint8_t d = CS_MM_NONE;
+  uint64_t total = 0;
+  cs_status s = cs_fm_locate_best_mismatch(h_.get(), p, pattern.size(), k, &d, nullptr, 0, &total);
+  if (s != CS_OK && s != CS_ERR_CAPACITY) raise(s);
+  if (total) {
+    res.second.resize(total);
+    s = cs_fm_locate_best_mismatch(h_.get(), p, pattern.size(), k, &d, res.second.data(), total, &total);
+    if (s != CS_OK) raise(s);
+  }
+  res.first = d == CS_MM_NONE ? -1 : (int)d;
   return res;
 }
 

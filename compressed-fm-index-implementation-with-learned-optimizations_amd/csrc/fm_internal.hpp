@@ -16,6 +16,7 @@
 #include "../../include/cs_fmindex_approx.h"
 #include "../../include/cs_fmindex_approx_locate.h"
 #include "../../include/cs_fmindex_approx_best.h"
+#include "../../include/cs_fmindex_approx_best_locate.h"
 #include "fm_device.hpp"
 
 struct cs_fm_index {
@@ -447,5 +448,27 @@ cs_status launch_locate_mm_emit(const cs_fm_index* h, const uint8_t* d_pats, con
                                 const uint64_t* d_out_offs, const MmLeafPlan& plan,
                                 uint64_t* d_out_pos, uint8_t* d_out_dist, uint32_t flags,
                                 hipStream_t st, hipEvent_t* ev = nullptr);
+
+// Best-stratum locate (cs_fmindex_approx_best_locate.h), in the same two steps.  Sizing: rounds
+// 0..k back to back (k_best_locate_mm; pending lists as launch_best_mm's, the resolved lists
+// in plan.res), the two scans, one read-back (the call's one synchronisation of st before the
+// overrun word's); d_best_dist[npat] and d_out_offs[npat + 1] are written.  Emitting: one
+// kernel per round with a non-empty resolved list, launch_locate_walk over all leaves into
+// d_out_pos[plan.total], then the overrun word as launch_locate_mm_emit.
+struct BestLeafPlan {
+  StreamBuf leaf_base;  // [npat + 1]: the exclusive scan of the patterns' leaf counts
+  StreamBuf res;        // [npat]: round r's resolved patterns at [bound[r], bound[r + 1])
+  uint64_t bound[CS_MM_MAX + 2] = {};
+  uint64_t nleaf = 0, total = 0;
+};
+cs_status launch_best_locate_mm_size(const cs_fm_index* h, const uint8_t* d_pats,
+                                     const uint64_t* d_offs, uint64_t npat, uint32_t k,
+                                     uint64_t fixed_m, uint8_t* d_best_dist, uint64_t* d_out_offs,
+                                     uint32_t flags, hipStream_t st, BestLeafPlan& plan);
+cs_status launch_best_locate_mm_emit(const cs_fm_index* h, const uint8_t* d_pats,
+                                     const uint64_t* d_offs, uint64_t npat, uint32_t k,
+                                     uint64_t fixed_m, const uint64_t* d_out_offs,
+                                     const BestLeafPlan& plan, uint64_t* d_out_pos, uint32_t flags,
+                                     hipStream_t st);
 
 }  // namespace fmx

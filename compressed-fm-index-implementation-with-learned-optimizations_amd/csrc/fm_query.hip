@@ -212,6 +212,101 @@ __global__ __launch_bounds__(kBlk) void k_locate_mm(DevIndex ix, const uint8_t* 
   }
 }
 
+// Best-stratum locate (cs_fm_locate_best_mismatch_device): round K of
+// launch_best_locate_mm_size / _emit, one pattern per lane; k_best_mm's rounds with
+// k_locate_mm's two passes.  The traversal is mm_leaves<E, 0, K> with kmax = K (K = 0: mm_rest,
+// no symbol list).  A pattern of round K has no hit below K, so its shallower subtrees die
+// where they died before and every leaf the sink sees is a non-empty one at depth K: exactly
+// stratum K, in the order k_locate_mm at the same bound visits those leaves.
+// Sizing (kEmit = false): round 0 runs over every pattern, round K >= 1 over the pending list
+// list_in[0 .. *len_in).  A lane with occurrences (in round 0 also an empty pattern over a
+// non-empty text, with no leaf) writes best_dist[q] = K, cnt_leaf[q], cnt_occ[q] and appends q
+// to the resolved list res at *res_len, a cursor shared by all rounds (the launch records it
+// after each round, so round K's patterns are one slice of res).  A lane without a hit appends
+// q to list_out or, in the last round, writes (CS_MM_NONE, 0, 0).  So every pattern's three
+// values are written exactly once over the rounds.  Both appends are k_best_mm's: one ballot
+// and one atomicAdd per wave, the lanes scatter by their prefix popcount.  A list's order
+// therefore depends on which wave's atomicAdd lands first; the result does not, since every
+// output is indexed by q.  The grid covers npat; a block whose first entry is at or past the
+// list's length returns before it stages anything, a block-uniform test ahead of every barrier.
+// Emitting (kEmit = true): over round K's resolved slice list_in[0 .. nlist) (nlist from the
+// host, the grid covers it; len_in and the append arguments are unused); cnt_leaf / cnt_occ
+// hold the exclusive scans (the second is d_out_offs) and leaf l of the pattern gets
+// leaf_sp[l], leaf_off[l] and a distance byte nobody reads.  A lane never writes at or past
+// its pattern's leaf end (LeafSink::leaf).  Nothing waits on another wave or block, and every
+// loop is bounded as mm_leaves' are.  list_out and res hold npat entries each; a pattern
+// enters at most one of them per round and res at most once.
+template <class E, int K, bool kEmit>
+__global__ __launch_bounds__(kBlk) void k_best_locate_mm(
+    DevIndex ix, const uint8_t* __restrict__ pats, const uint64_t* __restrict__ offs, uint64_t npat,
+    uint64_t fixed_m, bool last, const uint64_t* __restrict__ list_in,
+    const unsigned long long* __restrict__ len_in, uint64_t nlist, uint64_t* __restrict__ list_out,
+    unsigned long long* len_out, uint64_t* __restrict__ res, unsigned long long* res_len,
+    uint8_t* __restrict__ best_dist, uint64_t* cnt_leaf, uint64_t* cnt_occ,
+    uint64_t* __restrict__ leaf_sp, uint64_t* __restrict__ leaf_off, uint8_t* __restrict__ leaf_dist) {
+  if constexpr (!kEmit) {
+    nlist = npat;
+    if constexpr (K > 0) {
+      nlist = *len_in;
+      if (blockIdx.x * (uint64_t)blockDim.x >= nlist) return;
+    }
+  }
+  __shared__ NodeTable T;
+  __shared__ SymList L;
+  load_table(T, ix.table);
+  __syncthreads();
+  if constexpr (K > 0) list_symbols(L, T);
+  const uint64_t e = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  // (no early return for the lanes past the list: the appends below are per wave)
+  uint64_t q = 0;
+  bool hit = false, miss = false;
+  if (e < nlist) {
+    if constexpr (K > 0 || kEmit) q = list_in[e];
+    else q = e;
+    const uint64_t o0 = offs ? offs[q] : q * fixed_m, m = offs ? offs[q + 1] - o0 : fixed_m;
+    LeafSink sink;
+    sink.nleaf = kEmit ? cnt_leaf[q] : 0;
+    sink.nocc = kEmit ? cnt_occ[q] : 0;
+    sink.end = kEmit ? cnt_leaf[q + 1] : 0;
+    sink.leaf_sp = kEmit ? leaf_sp : nullptr;
+    sink.leaf_off = leaf_off;
+    sink.leaf_dist = leaf_dist;
+    if (m != 0 && ix.n != 0) {
+      if constexpr (K == 0) mm_rest<E>(ix, T, pats + o0, m, 0, m, 0, ix.n, sink);
+      else mm_leaves<E, 0, K>(ix, T, L, pats + o0, m, (uint32_t)K, m, 0, ix.n, sink);
+    }
+    if constexpr (!kEmit) {
+      hit = sink.nocc != 0 || (K == 0 && m == 0 && ix.n != 0);  // fm_index.cpp:80
+      miss = !hit && !last;
+      if (!miss) {
+        best_dist[q] = hit ? (uint8_t)K : (uint8_t)CS_MM_NONE;
+        cnt_leaf[q] = sink.nleaf;
+        cnt_occ[q] = sink.nocc;
+      }
+    }
+  }
+  if constexpr (!kEmit) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t below = (1ull << lane) - 1ull;
+    const uint64_t bal_hit = __ballot(hit);
+    if (bal_hit) {  // wave-uniform
+      const uint32_t lead = (uint32_t)__ffsll((unsigned long long)bal_hit) - 1u;
+      unsigned long long base = 0;
+      if (lane == lead) base = atomicAdd(res_len, (unsigned long long)__popcll(bal_hit));
+      base = __shfl(base, (int)lead);
+      if (hit) res[base + (uint32_t)__popcll(bal_hit & below)] = q;
+    }
+    const uint64_t bal = __ballot(miss);
+    if (bal) {  // wave-uniform
+      const uint32_t lead = (uint32_t)__ffsll((unsigned long long)bal) - 1u;
+      unsigned long long base = 0;
+      if (lane == lead) base = atomicAdd(len_out, (unsigned long long)__popcll(bal));
+      base = __shfl(base, (int)lead);
+      if (miss) list_out[base + (uint32_t)__popcll(bal & below)] = q;
+    }
+  }
+}
+
 // d_out_dist[leaf_off[l] .. leaf_off[l + 1]) = leaf_dist[l].  A lane fills a leaf of at most
 // kLocSmall occurrences; the block's wider leaves (a 1-mer's holds n / 4 rows) are listed in
 // LDS and filled by the whole block, one after the other.
@@ -4305,6 +4400,110 @@ cs_status launch_locate_mm_emit(const cs_fm_index* h, const uint8_t* d_pats, con
     FMX_HIP(hipGetLastError());
   }
   if (ev) FMX_HIP(hipEventRecord(ev[5], st));
+  return check_locate_error(h, e, st);
+}
+
+cs_status launch_best_locate_mm_size(const cs_fm_index* h, const uint8_t* d_pats,
+                                     const uint64_t* d_offs, uint64_t npat, uint32_t k,
+                                     uint64_t fixed_m, uint8_t* d_best_dist, uint64_t* d_out_offs,
+                                     uint32_t flags, hipStream_t st, BestLeafPlan& plan) {
+  // control words: [0, CS_MM_MAX) the pending lists' lengths (round r reads list r - 1 and
+  // appends to list r, the lists alternate between the halves of `lists`), then the resolved
+  // list's cursor, and what the host reads back in one copy: bound[0 .. CS_MM_MAX + 2) (those
+  // past k + 1 stay 0 and are not used), total, nleaf
+  constexpr uint32_t kCur = CS_MM_MAX, kBound = kCur + 1, kTotal = kBound + CS_MM_MAX + 2,
+                     kWords = kTotal + 2;
+  StreamBuf cnt_leaf, cnt_occ, lists, ctl, tmp;
+  FMX_HIP(cnt_leaf.alloc((npat + 1) * 8, st));
+  FMX_HIP(cnt_occ.alloc((npat + 1) * 8, st));
+  FMX_HIP(plan.leaf_base.alloc((npat + 1) * 8, st));
+  FMX_HIP(plan.res.alloc(npat * 8, st));
+  if (k) FMX_HIP(lists.alloc(2 * npat * 8, st));
+  FMX_HIP(ctl.alloc(kWords * 8, st));
+  FMX_HIP(hipMemsetAsync(ctl.p, 0, kWords * 8, st));
+  // scan slots for the totals
+  FMX_HIP(hipMemsetAsync(cnt_leaf.as<uint64_t>() + npat, 0, 8, st));
+  FMX_HIP(hipMemsetAsync(cnt_occ.as<uint64_t>() + npat, 0, 8, st));
+  const DevIndex ix = query_dev(h, call_flags(h, flags));
+  unsigned long long* const w = ctl.as<unsigned long long>();
+  // a round's list length is known on the device only: every round's grid covers npat
+  const unsigned g = grid_for(npat, kBlk, 0xFFFFFFFFu);
+  hipError_t err = hipSuccess;
+  with_engine(h->line_fmt, [&](auto engine) {
+    using E = typename decltype(engine)::type;
+    for (uint32_t r = 0; r <= k && err == hipSuccess; ++r) {
+      uint64_t* const in = r ? lists.as<uint64_t>() + ((r - 1) & 1) * npat : nullptr;
+      uint64_t* const out = r < k ? lists.as<uint64_t>() + (r & 1) * npat : nullptr;
+      with_int<0, 1, 2, 3>((int)r, [&](auto K) {
+        k_best_locate_mm<E, K, false><<<g, kBlk, 0, st>>>(
+            ix, d_pats, d_offs, npat, fixed_m, /*last*/ r == k, in, r ? w + (r - 1) : nullptr, 0, out,
+            r < k ? w + r : nullptr, plan.res.as<uint64_t>(), w + kCur, d_best_dist,
+            cnt_leaf.as<uint64_t>(), cnt_occ.as<uint64_t>(), nullptr, nullptr, nullptr);
+      });
+      // round r's patterns are res[bound[r] .. bound[r + 1])
+      err = hipMemcpyAsync(w + kBound + r + 1, w + kCur, 8, hipMemcpyDeviceToDevice, st);
+    }
+  });
+  FMX_HIP(err);
+  FMX_HIP(hipGetLastError());
+  // the two exclusive scans (one temporary serves both: same type, same length)
+  size_t tb = 0;
+  FMX_HIP(rocprim::exclusive_scan(nullptr, tb, cnt_occ.as<uint64_t>(), d_out_offs, (uint64_t)0,
+                                  npat + 1, rocprim::plus<uint64_t>(), st));
+  FMX_HIP(tmp.alloc(tb, st));
+  FMX_HIP(rocprim::exclusive_scan(tmp.p, tb, cnt_occ.as<uint64_t>(), d_out_offs, (uint64_t)0,
+                                  npat + 1, rocprim::plus<uint64_t>(), st));
+  FMX_HIP(rocprim::exclusive_scan(tmp.p, tb, cnt_leaf.as<uint64_t>(), plan.leaf_base.as<uint64_t>(),
+                                  (uint64_t)0, npat + 1, rocprim::plus<uint64_t>(), st));
+  // one read-back: the bounds and the two totals
+  FMX_HIP(hipMemcpyAsync(w + kTotal, d_out_offs + npat, 8, hipMemcpyDeviceToDevice, st));
+  FMX_HIP(hipMemcpyAsync(w + kTotal + 1, plan.leaf_base.as<uint64_t>() + npat, 8,
+                         hipMemcpyDeviceToDevice, st));
+  uint64_t back[CS_MM_MAX + 4];
+  FMX_HIP(hipMemcpyAsync(back, w + kBound, sizeof back, hipMemcpyDeviceToHost, st));
+  FMX_HIP(hipStreamSynchronize(st));
+  for (uint32_t r = 0; r < CS_MM_MAX + 2; ++r) plan.bound[r] = back[r];
+  plan.total = back[CS_MM_MAX + 2];
+  plan.nleaf = back[CS_MM_MAX + 3];
+  return CS_OK;
+}
+
+cs_status launch_best_locate_mm_emit(const cs_fm_index* h, const uint8_t* d_pats,
+                                     const uint64_t* d_offs, uint64_t npat, uint32_t k,
+                                     uint64_t fixed_m, const uint64_t* d_out_offs,
+                                     const BestLeafPlan& plan, uint64_t* d_out_pos, uint32_t flags,
+                                     hipStream_t st) {
+  const uint64_t nleaf = plan.nleaf, total = plan.total;
+  StreamBuf leaf_sp, leaf_off, leaf_dist, err;
+  FMX_HIP(leaf_sp.alloc(nleaf * 8, st));
+  FMX_HIP(leaf_off.alloc((nleaf + 1) * 8, st));
+  FMX_HIP(leaf_dist.alloc(nleaf, st));  // LeafSink's distance per leaf: all K in round K, unread
+  FMX_HIP(err.alloc(8, st));
+  FMX_HIP(hipMemsetAsync(err.p, 0xFF, 8, st));
+  const DevIndex ix = query_dev(h, call_flags(h, flags));
+  with_engine(h->line_fmt, [&](auto engine) {
+    using E = typename decltype(engine)::type;
+    for (uint32_t r = 0; r <= k; ++r) {
+      const uint64_t nres = plan.bound[r + 1] - plan.bound[r];
+      if (!nres) continue;
+      with_int<0, 1, 2, 3>((int)r, [&](auto K) {
+        k_best_locate_mm<E, K, true><<<grid_for(nres, kBlk, 0xFFFFFFFFu), kBlk, 0, st>>>(
+            ix, d_pats, d_offs, npat, fixed_m, false, plan.res.as<uint64_t>() + plan.bound[r], nullptr,
+            nres, nullptr, nullptr, nullptr, nullptr, nullptr, plan.leaf_base.as<uint64_t>(),
+            const_cast<uint64_t*>(d_out_offs), leaf_sp.as<uint64_t>(), leaf_off.as<uint64_t>(),
+            leaf_dist.as<uint8_t>());
+      });
+    }
+  });
+  FMX_HIP(hipGetLastError());
+  // the closing leaf_off[nleaf] = total
+  FMX_HIP(hipMemcpyAsync(leaf_off.as<uint64_t>() + nleaf, d_out_offs + npat, 8, hipMemcpyDeviceToDevice, st));
+  // the positions: the exact locate's phase 2 with the leaves as its patterns; the leaves are
+  // in pattern order, so the output is in batch order
+  unsigned long long* e = err.as<unsigned long long>();
+  cs_status s = launch_locate_walk(h, leaf_sp.as<uint64_t>(), leaf_off.as<uint64_t>(), nleaf, total,
+                                   d_out_pos, st, e, flags);
+  if (s != CS_OK) return s;
   return check_locate_error(h, e, st);
 }
 

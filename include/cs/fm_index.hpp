@@ -4,7 +4,7 @@
 // exceptions as cs::FMIndex (src/api/fm_index.hpp:11-67); the work runs on the GPU
 // through the C ABI in cs_fmindex.h (implementation: csrc/fm_facade.cpp inside
 // libcs_fmindex.so).  Additions: count_batch / locate_batch (one launch for many
-// patterns), count_mismatches / locate_mismatches / best_mismatch (occurrences within k substitutions, their positions, and the smallest distance with a hit), save_directory (the on-disk format open_directory reads), handle()
+// patterns), count_mismatches / locate_mismatches / best_mismatch / locate_best_mismatch (occurrences within k substitutions, their positions, the smallest distance with a hit, and the positions at that distance), save_directory (the on-disk format open_directory reads), handle()
 // for the raw ABI, borrow() to wrap an ABI handle and serve() (resident
 // single-pattern server).  Errors are
 // std::runtime_error with the reference's message text ("locate: LF walk exceeded
@@ -66,6 +66,11 @@ class FMIndex {
   // order).  An empty pattern has none, as locate().  Throws as count_mismatches does.
   std::vector<std::pair<uint64_t, uint8_t>> locate_mismatches(std::string_view pattern,
                                                               unsigned k) const;
+  // Best-stratum locate (cs_fmindex_approx_best_locate.h): best_mismatch's distance and the
+  // positions at that distance only, in locate_mismatches' order; (-1, {}) when there is none
+  // within k, (0, {}) for an empty pattern over a non-empty text.  Throws as best_mismatch does.
+  std::pair<int, std::vector<uint64_t>> locate_best_mismatch(std::string_view pattern,
+                                                             unsigned k) const;
 
   // Serving mode for single-pattern count(): a resident wave answers from a pinned
   // mailbox instead of one kernel launch per call (cs_fm_serve_start / _stop).
