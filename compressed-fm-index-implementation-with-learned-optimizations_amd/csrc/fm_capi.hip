@@ -1057,48 +1057,64 @@ cs_status cs_fm_count(const cs_fm_index* h, const uint8_t* pattern, uint64_t m, 
   return cs_fm_count_batch(h, pattern, offs, 1, out, nullptr);
 }
 
-// ---- count within k mismatches (include/cs_fmindex_approx.h) ----
-static cs_status mismatch_bound_ok(uint32_t k) {
+// ---- search within k mismatches (include/cs_fmindex_approx.h, _approx_best.h, _approx_locate.h,
+// _approx_best_locate.h) ----
+static cs_status null_batch_pointer() {
+  set_error("null batch pointer");
+  return CS_ERR_INVALID;
+}
+
+// What every entry point of the family checks first, in this order: the handle (entering its
+// device), the bound k, and the entry point's own pointer arguments (null_arg).
+static cs_status mismatch_enter(const cs_fm_index* h, DeviceScope& dscope, uint32_t k, bool null_arg) {
+  cs_status s = check_handle(h, dscope);
+  if (s != CS_OK) return s;
   if (k > CS_MM_MAX) {
     set_error("mismatch bound k must be at most CS_MM_MAX = " + std::to_string(CS_MM_MAX));
     return CS_ERR_INVALID;
   }
-  return CS_OK;
+  return null_arg ? null_batch_pointer() : CS_OK;
+}
+
+// The device forms: then the batch with a null d_pats (null_pats_ok).
+static cs_status mismatch_enter_device(const cs_fm_index* h, DeviceScope& dscope, uint32_t k, bool null_arg,
+                                       const uint8_t* d_pats, const uint64_t* d_offs, uint64_t npat,
+                                       hipStream_t st) {
+  cs_status s = mismatch_enter(h, dscope, k, null_arg);
+  return s == CS_OK ? null_pats_ok(d_pats, d_offs, npat, st) : s;
+}
+
+// The host batch forms, after mismatch_enter and with npat >= 1: the batch's pointers (null_out:
+// an output every pattern writes), its offsets, then the batch staged into HBM.
+static cs_status mismatch_stage(const cs_fm_index* h, const uint8_t* pats, const uint64_t* offs,
+                                uint64_t npat, bool null_out, StagedBatch& b, hipStream_t st) {
+  if (!offs || null_out || (!pats && offs[npat] != offs[0])) return null_batch_pointer();
+  cs_status s = check_offsets(offs, npat);
+  return s == CS_OK ? b.load(h, pats, offs, npat, st) : s;
 }
 
 cs_status cs_fm_count_mismatch_device(const cs_fm_index* h, const uint8_t* d_pats,
                                       const uint64_t* d_offs, uint64_t fixed_m, uint64_t npat,
                                       uint32_t k, uint64_t* d_hist, uint32_t flags, void* stream) {
   DeviceScope dscope;
-  cs_status s = check_handle(h, dscope);
+  hipStream_t st = (hipStream_t)stream;
+  cs_status s = mismatch_enter_device(h, dscope, k, npat && (!d_hist || (!d_pats && !d_offs && fixed_m)),
+                                      d_pats, d_offs, npat, st);
   if (s != CS_OK) return s;
-  if ((s = mismatch_bound_ok(k)) != CS_OK) return s;
-  if (npat && (!d_hist || (!d_pats && !d_offs && fixed_m))) {
-    set_error("null batch pointer");
-    return CS_ERR_INVALID;
-  }
-  if ((s = null_pats_ok(d_pats, d_offs, npat, (hipStream_t)stream)) != CS_OK) return s;
-  return launch_count_mm(h, d_pats, d_offs, npat, k, d_hist, flags, (hipStream_t)stream,
-                         d_offs ? 0 : fixed_m);
+  return launch_count_mm(h, d_pats, d_offs, npat, k, d_hist, flags, st, d_offs ? 0 : fixed_m);
 }
 
 cs_status cs_fm_count_mismatch_batch(const cs_fm_index* h, const uint8_t* pats, const uint64_t* offs,
                                      uint64_t npat, uint32_t k, uint64_t* out_hist, void* stream) {
   DeviceScope dscope;
-  cs_status s = check_handle(h, dscope);
+  cs_status s = mismatch_enter(h, dscope, k, false);
   if (s != CS_OK) return s;
-  if ((s = mismatch_bound_ok(k)) != CS_OK) return s;
   if (!npat) return CS_OK;
-  if (!offs || !out_hist || (!pats && offs[npat] != offs[0])) {
-    set_error("null batch pointer");
-    return CS_ERR_INVALID;
-  }
-  if ((s = check_offsets(offs, npat)) != CS_OK) return s;
   hipStream_t st = (hipStream_t)stream;
   const uint64_t out_bytes = npat * (k + 1) * 8;
   HostPin pin_out;
   StagedBatch b;
-  if ((s = b.load(h, pats, offs, npat, st)) != CS_OK) return s;
+  if ((s = mismatch_stage(h, pats, offs, npat, !out_hist, b, st)) != CS_OK) return s;
   StreamBuf d_hist;
   FMX_HIP(d_hist.alloc(out_bytes, st));
   pin_out.pin(h, out_hist, out_bytes, st);
@@ -1116,41 +1132,31 @@ cs_status cs_fm_count_mismatch(const cs_fm_index* h, const uint8_t* pattern, uin
   return cs_fm_count_mismatch_batch(h, pattern, offs, 1, k, out_hist, nullptr);
 }
 
-// ---- best stratum within k mismatches (include/cs_fmindex_approx_best.h) ----
 cs_status cs_fm_best_mismatch_device(const cs_fm_index* h, const uint8_t* d_pats,
                                      const uint64_t* d_offs, uint64_t fixed_m, uint64_t npat,
                                      uint32_t k, uint8_t* d_best_dist, uint64_t* d_best_count,
                                      uint32_t flags, void* stream) {
   DeviceScope dscope;
-  cs_status s = check_handle(h, dscope);
+  hipStream_t st = (hipStream_t)stream;
+  cs_status s = mismatch_enter_device(
+      h, dscope, k, npat && (!d_best_dist || !d_best_count || (!d_pats && !d_offs && fixed_m)), d_pats,
+      d_offs, npat, st);
   if (s != CS_OK) return s;
-  if ((s = mismatch_bound_ok(k)) != CS_OK) return s;
-  if (npat && (!d_best_dist || !d_best_count || (!d_pats && !d_offs && fixed_m))) {
-    set_error("null batch pointer");
-    return CS_ERR_INVALID;
-  }
-  if ((s = null_pats_ok(d_pats, d_offs, npat, (hipStream_t)stream)) != CS_OK) return s;
-  return launch_best_mm(h, d_pats, d_offs, npat, k, d_best_dist, d_best_count, flags,
-                        (hipStream_t)stream, d_offs ? 0 : fixed_m);
+  return launch_best_mm(h, d_pats, d_offs, npat, k, d_best_dist, d_best_count, flags, st,
+                        d_offs ? 0 : fixed_m);
 }
 
 cs_status cs_fm_best_mismatch_batch(const cs_fm_index* h, const uint8_t* pats, const uint64_t* offs,
                                     uint64_t npat, uint32_t k, uint8_t* out_dist, uint64_t* out_count,
                                     void* stream) {
   DeviceScope dscope;
-  cs_status s = check_handle(h, dscope);
+  cs_status s = mismatch_enter(h, dscope, k, false);
   if (s != CS_OK) return s;
-  if ((s = mismatch_bound_ok(k)) != CS_OK) return s;
   if (!npat) return CS_OK;
-  if (!offs || !out_dist || !out_count || (!pats && offs[npat] != offs[0])) {
-    set_error("null batch pointer");
-    return CS_ERR_INVALID;
-  }
-  if ((s = check_offsets(offs, npat)) != CS_OK) return s;
   hipStream_t st = (hipStream_t)stream;
   HostPin pin_dist, pin_count;
   StagedBatch b;
-  if ((s = b.load(h, pats, offs, npat, st)) != CS_OK) return s;
+  if ((s = mismatch_stage(h, pats, offs, npat, !out_dist || !out_count, b, st)) != CS_OK) return s;
   StreamBuf d_dist, d_count;
   FMX_HIP(d_dist.alloc(npat, st));
   FMX_HIP(d_count.alloc(npat * 8, st));
@@ -1171,23 +1177,19 @@ cs_status cs_fm_best_mismatch(const cs_fm_index* h, const uint8_t* pattern, uint
   return cs_fm_best_mismatch_batch(h, pattern, offs, 1, k, out_dist, out_count, nullptr);
 }
 
-// ---- locate within k mismatches (include/cs_fmindex_approx_locate.h) ----
-// the device batch; phase_ms: null, or the five phase times of cs_fm_locate_mismatch_phases_device
+// the device batch of the locate within k; phase_ms: null, or the five phase times of
+// cs_fm_locate_mismatch_phases_device
 static cs_status locate_mismatch_device(const cs_fm_index* h, const uint8_t* d_pats,
                                         const uint64_t* d_offs, uint64_t fixed_m, uint64_t npat,
                                         uint32_t k, uint64_t* d_out_offs, uint64_t* d_out_pos,
                                         uint8_t* d_out_dist, uint64_t cap, uint64_t* total,
                                         uint32_t flags, hipStream_t st, float* phase_ms) {
   DeviceScope dscope;
-  cs_status s = check_handle(h, dscope);
+  cs_status s = mismatch_enter_device(h, dscope, k,
+                                      !total || !d_out_offs || (cap && (!d_out_pos || !d_out_dist)) ||
+                                          (npat && !d_pats && !d_offs && fixed_m),
+                                      d_pats, d_offs, npat, st);
   if (s != CS_OK) return s;
-  if ((s = mismatch_bound_ok(k)) != CS_OK) return s;
-  if (!total || !d_out_offs || (cap && (!d_out_pos || !d_out_dist)) ||
-      (npat && !d_pats && !d_offs && fixed_m)) {
-    set_error("null batch pointer");
-    return CS_ERR_INVALID;
-  }
-  if ((s = null_pats_ok(d_pats, d_offs, npat, st)) != CS_OK) return s;
   struct Events {
     hipEvent_t e[6] = {};
     ~Events() {
@@ -1247,41 +1249,42 @@ cs_status cs_fm_locate_mismatch_phases_device(const cs_fm_index* h, const uint8_
                                 total, flags, (hipStream_t)stream, phase_ms);
 }
 
-cs_status cs_fm_locate_mismatch_batch(const cs_fm_index* h, const uint8_t* pats, const uint64_t* offs,
-                                      uint64_t npat, uint32_t k, uint64_t* out_offs, uint64_t* out_pos,
-                                      uint8_t* out_dist, uint64_t cap, uint64_t* total, void* stream) {
+// The host batch of both locates, one capacity protocol: size(batch, d_out_offs, d_dist), *total
+// and out_offs[npat + 1] out, the capacity test — the position step does not run past it —
+// then emit(batch, d_out_offs, d_pos, d_dist) and the positions out.  out_dist is the call's
+// byte output: one byte per pattern, out with the offsets (dist_per_pattern: the strata of the
+// best-stratum locate), or one per occurrence, out with the positions (the distances of the
+// locate within k).  plan: the caller's, filled by size.  (A HostPin of no bytes holds no page
+// and copies nothing.)
+extern "C++" {  // (a template, inside the C ABI's linkage block)
+template <class Size, class Emit>
+static cs_status locate_mismatch_batch(const cs_fm_index* h, const uint8_t* pats, const uint64_t* offs,
+                                       uint64_t npat, uint32_t k, uint8_t* out_dist, bool dist_per_pattern,
+                                       uint64_t* out_offs, uint64_t* out_pos, uint64_t cap,
+                                       uint64_t* total, hipStream_t st, const MmLeafPlan& plan, Size size,
+                                       Emit emit) {
   DeviceScope dscope;
-  cs_status s = check_handle(h, dscope);
+  cs_status s = mismatch_enter(h, dscope, k, !total || !out_offs);
   if (s != CS_OK) return s;
-  if ((s = mismatch_bound_ok(k)) != CS_OK) return s;
-  if (!total || !out_offs) {
-    set_error("null batch pointer");
-    return CS_ERR_INVALID;
-  }
   *total = 0;
   if (!npat) {
     out_offs[0] = 0;
     return CS_OK;
   }
-  if (!offs || (!pats && offs[npat] != offs[0])) {
-    set_error("null batch pointer");
-    return CS_ERR_INVALID;
-  }
-  if ((s = check_offsets(offs, npat)) != CS_OK) return s;
-  hipStream_t st = (hipStream_t)stream;
   StagedBatch b;
-  if ((s = b.load(h, pats, offs, npat, st)) != CS_OK) return s;
-  StreamBuf d_oo;
+  if ((s = mismatch_stage(h, pats, offs, npat, dist_per_pattern && !out_dist, b, st)) != CS_OK) return s;
+  const uint64_t n_sized = dist_per_pattern ? npat : 0;  // out_dist's bytes known after sizing
+  StreamBuf d_oo, d_dist;
   FMX_HIP(d_oo.alloc((npat + 1) * 8, st));
-  MmLeafPlan plan;
-  if ((s = launch_locate_mm_size(h, b.pats.as<uint8_t>(), b.offs.as<uint64_t>(), npat, k, 0,
-                                 d_oo.as<uint64_t>(), 0, st, plan)) != CS_OK)
-    return s;
+  if (n_sized) FMX_HIP(d_dist.alloc(n_sized, st));
+  if ((s = size(b, d_oo.as<uint64_t>(), d_dist.as<uint8_t>())) != CS_OK) return s;
   *total = plan.total;
   {
-    HostPin po;
+    HostPin po, pd;
     po.pin(h, out_offs, (npat + 1) * 8, st);
+    pd.pin(h, out_dist, n_sized, st);
     FMX_HIP(po.copy(out_offs, d_oo.p, (npat + 1) * 8, false, st));
+    FMX_HIP(pd.copy(out_dist, d_dist.p, n_sized, false, st));
   }
   FMX_HIP(hipStreamSynchronize(st));
   if (plan.total > cap) {  // after the sizing step: the position phase does not run
@@ -1289,23 +1292,40 @@ cs_status cs_fm_locate_mismatch_batch(const cs_fm_index* h, const uint8_t* pats,
     return CS_ERR_CAPACITY;
   }
   if (!plan.total) return CS_OK;
-  if (!out_pos || !out_dist) {
+  const uint64_t n_emit = dist_per_pattern ? 0 : plan.total;  // out_dist's bytes that come with the positions
+  if (!out_pos || (n_emit && !out_dist)) {
     set_error("null output buffer");
     return CS_ERR_INVALID;
   }
-  StreamBuf d_pos, d_dist;
+  StreamBuf d_pos;
   FMX_HIP(d_pos.alloc(plan.total * 8, st));
-  FMX_HIP(d_dist.alloc(plan.total, st));
-  s = launch_locate_mm_emit(h, b.pats.as<uint8_t>(), b.offs.as<uint64_t>(), npat, k, 0,
-                            d_oo.as<uint64_t>(), plan, d_pos.as<uint64_t>(), d_dist.as<uint8_t>(), 0, st);
-  if (s != CS_OK) return s;
+  if (n_emit) FMX_HIP(d_dist.alloc(n_emit, st));
+  if ((s = emit(b, d_oo.as<uint64_t>(), d_pos.as<uint64_t>(), d_dist.as<uint8_t>())) != CS_OK) return s;
   HostPin pp, pd;
   pp.pin(h, out_pos, plan.total * 8, st);
-  pd.pin(h, out_dist, plan.total, st);
+  pd.pin(h, out_dist, n_emit, st);
   FMX_HIP(pp.copy(out_pos, d_pos.p, plan.total * 8, false, st));
-  FMX_HIP(pd.copy(out_dist, d_dist.p, plan.total, false, st));
+  FMX_HIP(pd.copy(out_dist, d_dist.p, n_emit, false, st));
   FMX_HIP(hipStreamSynchronize(st));
   return CS_OK;
+}
+}  // extern "C++"
+
+cs_status cs_fm_locate_mismatch_batch(const cs_fm_index* h, const uint8_t* pats, const uint64_t* offs,
+                                      uint64_t npat, uint32_t k, uint64_t* out_offs, uint64_t* out_pos,
+                                      uint8_t* out_dist, uint64_t cap, uint64_t* total, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  MmLeafPlan plan;
+  return locate_mismatch_batch(
+      h, pats, offs, npat, k, out_dist, /*dist_per_pattern*/ false, out_offs, out_pos, cap, total, st, plan,
+      [&](const StagedBatch& b, uint64_t* d_oo, uint8_t*) {
+        return launch_locate_mm_size(h, b.pats.as<uint8_t>(), b.offs.as<uint64_t>(), npat, k, 0, d_oo, 0, st,
+                                     plan);
+      },
+      [&](const StagedBatch& b, const uint64_t* d_oo, uint64_t* d_pos, uint8_t* d_dist) {
+        return launch_locate_mm_emit(h, b.pats.as<uint8_t>(), b.offs.as<uint64_t>(), npat, k, 0, d_oo, plan,
+                                     d_pos, d_dist, 0, st);
+      });
 }
 
 cs_status cs_fm_locate_mismatch(const cs_fm_index* h, const uint8_t* pattern, uint64_t m, uint32_t k,
@@ -1324,22 +1344,19 @@ cs_status cs_fm_locate_mismatch(const cs_fm_index* h, const uint8_t* pattern, ui
   return s;
 }
 
-// ---- best-stratum locate (include/cs_fmindex_approx_best_locate.h) ----
 cs_status cs_fm_locate_best_mismatch_device(const cs_fm_index* h, const uint8_t* d_pats,
                                             const uint64_t* d_offs, uint64_t fixed_m, uint64_t npat,
                                             uint32_t k, uint8_t* d_best_dist, uint64_t* d_out_offs,
                                             uint64_t* d_out_pos, uint64_t cap, uint64_t* total,
                                             uint32_t flags, void* stream) {
   DeviceScope dscope;
-  cs_status s = check_handle(h, dscope);
+  cs_status s = mismatch_enter(h, dscope, k,
+                               !total || !d_out_offs || (cap && !d_out_pos) ||
+                                   (npat && (!d_best_dist || (!d_pats && !d_offs && fixed_m))));
   if (s != CS_OK) return s;
-  if ((s = mismatch_bound_ok(k)) != CS_OK) return s;
-  if (!total || !d_out_offs || (cap && !d_out_pos) ||
-      (npat && (!d_best_dist || (!d_pats && !d_offs && fixed_m)))) {
-    set_error("null batch pointer");
-    return CS_ERR_INVALID;
-  }
   hipStream_t st = (hipStream_t)stream;
+  // (*total and an empty batch's offsets are written before the batch is looked at, so this
+  // form takes the two halves of mismatch_enter_device apart)
   *total = 0;
   if (!npat) {
     FMX_HIP(hipMemsetAsync(d_out_offs, 0, 8, st));
@@ -1365,62 +1382,18 @@ cs_status cs_fm_locate_best_mismatch_batch(const cs_fm_index* h, const uint8_t* 
                                            const uint64_t* offs, uint64_t npat, uint32_t k,
                                            uint8_t* out_dist, uint64_t* out_offs, uint64_t* out_pos,
                                            uint64_t cap, uint64_t* total, void* stream) {
-  DeviceScope dscope;
-  cs_status s = check_handle(h, dscope);
-  if (s != CS_OK) return s;
-  if ((s = mismatch_bound_ok(k)) != CS_OK) return s;
-  if (!total || !out_offs) {
-    set_error("null batch pointer");
-    return CS_ERR_INVALID;
-  }
-  *total = 0;
-  if (!npat) {
-    out_offs[0] = 0;
-    return CS_OK;
-  }
-  if (!offs || !out_dist || (!pats && offs[npat] != offs[0])) {
-    set_error("null batch pointer");
-    return CS_ERR_INVALID;
-  }
-  if ((s = check_offsets(offs, npat)) != CS_OK) return s;
   hipStream_t st = (hipStream_t)stream;
-  StagedBatch b;
-  if ((s = b.load(h, pats, offs, npat, st)) != CS_OK) return s;
-  StreamBuf d_oo, d_dist;
-  FMX_HIP(d_oo.alloc((npat + 1) * 8, st));
-  FMX_HIP(d_dist.alloc(npat, st));
   BestLeafPlan plan;
-  if ((s = launch_best_locate_mm_size(h, b.pats.as<uint8_t>(), b.offs.as<uint64_t>(), npat, k, 0,
-                                      d_dist.as<uint8_t>(), d_oo.as<uint64_t>(), 0, st, plan)) != CS_OK)
-    return s;
-  *total = plan.total;
-  {
-    HostPin po, pd;
-    po.pin(h, out_offs, (npat + 1) * 8, st);
-    pd.pin(h, out_dist, npat, st);
-    FMX_HIP(po.copy(out_offs, d_oo.p, (npat + 1) * 8, false, st));
-    FMX_HIP(pd.copy(out_dist, d_dist.p, npat, false, st));
-  }
-  FMX_HIP(hipStreamSynchronize(st));
-  if (plan.total > cap) {  // after the sizing step: the position phase does not run
-    set_error("locate output capacity too small");
-    return CS_ERR_CAPACITY;
-  }
-  if (!plan.total) return CS_OK;
-  if (!out_pos) {
-    set_error("null output buffer");
-    return CS_ERR_INVALID;
-  }
-  StreamBuf d_pos;
-  FMX_HIP(d_pos.alloc(plan.total * 8, st));
-  s = launch_best_locate_mm_emit(h, b.pats.as<uint8_t>(), b.offs.as<uint64_t>(), npat, k, 0,
-                                 d_oo.as<uint64_t>(), plan, d_pos.as<uint64_t>(), 0, st);
-  if (s != CS_OK) return s;
-  HostPin pp;
-  pp.pin(h, out_pos, plan.total * 8, st);
-  FMX_HIP(pp.copy(out_pos, d_pos.p, plan.total * 8, false, st));
-  FMX_HIP(hipStreamSynchronize(st));
-  return CS_OK;
+  return locate_mismatch_batch(
+      h, pats, offs, npat, k, out_dist, /*dist_per_pattern*/ true, out_offs, out_pos, cap, total, st, plan,
+      [&](const StagedBatch& b, uint64_t* d_oo, uint8_t* d_best) {
+        return launch_best_locate_mm_size(h, b.pats.as<uint8_t>(), b.offs.as<uint64_t>(), npat, k, 0, d_best,
+                                          d_oo, 0, st, plan);
+      },
+      [&](const StagedBatch& b, const uint64_t* d_oo, uint64_t* d_pos, uint8_t*) {
+        return launch_best_locate_mm_emit(h, b.pats.as<uint8_t>(), b.offs.as<uint64_t>(), npat, k, 0, d_oo,
+                                          plan, d_pos, 0, st);
+      });
 }
 
 cs_status cs_fm_locate_best_mismatch(const cs_fm_index* h, const uint8_t* pattern, uint64_t m, uint32_t k,

@@ -89,7 +89,7 @@ struct cs_fm_index {
   uint32_t active_levels[256] = {};
   // Tuning defaults (CS_QT_* bits, cs_fmindex.h) and the host-batch chunk (patterns; 0 = the
   // default), read from the environment once when the handle is created (read_tuning); every
-  // query ORs its flags over `tune` (fm_query.hip call_flags) and reads no environment
+  // query ORs its flags over `tune` (call_flags below) and reads no environment
   uint32_t tune = 0;
   uint64_t host_chunk = 0;
   // the routed count: a wave lists its general searches for the list kernel when it holds
@@ -267,7 +267,11 @@ class BuildOptScope {
 // offending token in err for a malformed pair or a name no builder reads
 bool parse_build_options(const char* text, BuildOptions& o, std::string& err);
 
-// Query launches (fm_query.hip).
+// Query launches (fm_query.hip; the mismatch family's in fm_mismatch.hip).
+// the call's flags with the handle's tuning defaults
+inline uint32_t call_flags(const cs_fm_index* h, uint32_t flags) { return flags | h->tune; }
+// the index as one query sees it under the caller's query flags (fm_query.hip)
+fmx::DevIndex query_dev(const cs_fm_index* h, uint32_t flags);
 // d_offs == nullptr: npat patterns of length fixed_m at stride fixed_m; flags CS_Q_*
 cs_status launch_count(const cs_fm_index* h, const uint8_t* d_pats, const uint64_t* d_offs,
                        uint64_t npat, uint64_t* d_out, hipStream_t st, uint64_t fixed_m = 0,
@@ -455,11 +459,9 @@ cs_status launch_locate_mm_emit(const cs_fm_index* h, const uint8_t* d_pats, con
 // overrun word's); d_best_dist[npat] and d_out_offs[npat + 1] are written.  Emitting: one
 // kernel per round with a non-empty resolved list, launch_locate_walk over all leaves into
 // d_out_pos[plan.total], then the overrun word as launch_locate_mm_emit.
-struct BestLeafPlan {
-  StreamBuf leaf_base;  // [npat + 1]: the exclusive scan of the patterns' leaf counts
-  StreamBuf res;        // [npat]: round r's resolved patterns at [bound[r], bound[r + 1])
+struct BestLeafPlan : MmLeafPlan {
+  StreamBuf res;  // [npat]: round r's resolved patterns at [bound[r], bound[r + 1])
   uint64_t bound[CS_MM_MAX + 2] = {};
-  uint64_t nleaf = 0, total = 0;
 };
 cs_status launch_best_locate_mm_size(const cs_fm_index* h, const uint8_t* d_pats,
                                      const uint64_t* d_offs, uint64_t npat, uint32_t k,

@@ -55,287 +55,6 @@ __global__ __launch_bounds__(kBlk) void k_count(DevIndex ix, const uint8_t* __re
   store_count<0>(co, q, res);
 }
 
-// Count within k <= K mismatches, per distance (cs_fm_count_mismatch_device): one pattern per
-// lane, hist[q][d] = the summed exact counts of the strings at Hamming distance d from the
-// pattern, d = 0..k, by the depth-first search of mm_frame (fm_search.hpp) — at most K + 1
-// nested frames, all in registers.  Pattern bytes are read by index from global memory (they
-// stay in the caches; no length cap).  K = 1 also serves k = 0, the exact count.  A lane
-// whose tree is small idles until its wave's largest is done.
-template <class E, int K>
-__global__ __launch_bounds__(kBlk) void k_count_mm(DevIndex ix, const uint8_t* __restrict__ pats,
-                                                   const uint64_t* __restrict__ offs, uint64_t npat,
-                                                   uint32_t k, uint64_t* __restrict__ hist,
-                                                   uint64_t fixed_m) {
-  __shared__ NodeTable T;
-  __shared__ SymList L;
-  load_table(T, ix.table);
-  __syncthreads();
-  list_symbols(L, T);
-  const uint64_t q = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-  if (q >= npat) return;
-  const uint64_t o0 = offs ? offs[q] : q * fixed_m, m = offs ? offs[q + 1] - o0 : fixed_m;
-  uint64_t h[K + 1];
-#pragma unroll
-  for (int d = 0; d <= K; ++d) h[d] = 0;
-  if (m == 0) {
-    h[0] = ix.n;  // fm_index.cpp:80
-  } else if (ix.n != 0) {  // :81
-    if (K == 1 && k == 0) h[0] = count_pattern<E>(ix, T, pats + o0, m);
-    else {
-      SubPat<K> S;
-      S.b = pats + o0;
-#pragma unroll
-      for (int t = 0; t < K; ++t) S.pos[t] = ~0ull, S.sym[t] = 0;
-      mm_frame<E, 0, K>(ix, T, L, S, m, m, 0, ix.n, h);
-    }
-  }
-  uint64_t* const out = hist + q * (k + 1);
-#pragma unroll
-  for (int d = 0; d <= K; ++d)
-    if ((uint32_t)d <= k) out[d] = h[d];
-}
-
-// Best stratum (cs_fm_best_mismatch_device): round K of launch_best_mm, one pattern per lane.
-// Round 0 runs over every pattern (the exact count, empty patterns and n = 0 as in
-// k_count_mm); round K >= 1 over a pending list, list_in[0 .. *len_in): the patterns with no
-// hit at any distance below K, so mm_frame<E, 0, K>'s columns below K are zero and only h[K]
-// is taken.  A lane whose count is not zero writes (K, count); one without a hit appends its
-// pattern to list_out — one ballot and one atomicAdd on *len_out per wave, the lanes scatter
-// by their prefix popcount — or, in the last round, writes (CS_MM_NONE, 0).  So every
-// pattern's outputs are written exactly once over the rounds.  The grid is sized for npat (the
-// host never reads a length): a block whose first entry is at or past the list's length
-// returns before it stages anything, a block-uniform test ahead of every barrier.  Nothing
-// waits on another wave or block, and every loop is bounded as mm_frame's are.  list_out
-// holds npat entries and receives at most *len_in <= npat.
-template <class E, int K>
-__global__ __launch_bounds__(kBlk) void k_best_mm(DevIndex ix, const uint8_t* __restrict__ pats,
-                                                  const uint64_t* __restrict__ offs, uint64_t npat,
-                                                  uint64_t fixed_m, bool last,
-                                                  const uint64_t* __restrict__ list_in,
-                                                  const unsigned long long* __restrict__ len_in,
-                                                  uint64_t* __restrict__ list_out,
-                                                  unsigned long long* len_out,
-                                                  uint8_t* __restrict__ best_dist,
-                                                  uint64_t* __restrict__ best_count) {
-  uint64_t nlist = npat;
-  if constexpr (K > 0) {
-    nlist = *len_in;
-    if (blockIdx.x * (uint64_t)blockDim.x >= nlist) return;
-  }
-  __shared__ NodeTable T;
-  __shared__ SymList L;
-  load_table(T, ix.table);
-  __syncthreads();
-  if constexpr (K > 0) list_symbols(L, T);
-  const uint64_t e = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-  // (no early return for the lanes past the list: the append below is per wave)
-  uint64_t q = 0;
-  bool miss = false;
-  if (e < nlist) {
-    if constexpr (K > 0) q = list_in[e];
-    else q = e;
-    const uint64_t o0 = offs ? offs[q] : q * fixed_m, m = offs ? offs[q + 1] - o0 : fixed_m;
-    uint64_t cnt = 0;
-    if constexpr (K == 0) {
-      if (m == 0) cnt = ix.n;  // fm_index.cpp:80
-      else if (ix.n != 0) cnt = count_pattern<E>(ix, T, pats + o0, m);  // :81
-    } else if (m != 0 && ix.n != 0) {
-      uint64_t h[K + 1];
-#pragma unroll
-      for (int d = 0; d <= K; ++d) h[d] = 0;
-      SubPat<K> S;
-      S.b = pats + o0;
-#pragma unroll
-      for (int t = 0; t < K; ++t) S.pos[t] = ~0ull, S.sym[t] = 0;
-      mm_frame<E, 0, K>(ix, T, L, S, m, m, 0, ix.n, h);
-      cnt = h[K];
-    }
-    miss = cnt == 0 && !last;
-    if (!miss) {
-      best_dist[q] = cnt ? (uint8_t)K : (uint8_t)CS_MM_NONE;
-      best_count[q] = cnt;
-    }
-  }
-  const uint64_t bal = __ballot(miss);
-  if (bal) {  // wave-uniform
-    const uint32_t lane = threadIdx.x & 63, lead = (uint32_t)__ffsll((unsigned long long)bal) - 1u;
-    unsigned long long base = 0;
-    if (lane == lead) base = atomicAdd(len_out, (unsigned long long)__popcll(bal));
-    base = __shfl(base, (int)lead);
-    if (miss) list_out[base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = q;
-  }
-}
-
-// Locate within k <= K mismatches (cs_fm_locate_mismatch_device): one pattern per lane, the
-// traversal of mm_leaves (fm_search.hpp; k_count_mm's search with a leaf sink), run twice.
-// Sizing (kEmit = false): cnt_leaf[q] / cnt_occ[q] = the pattern's non-empty leaf ranges and
-// the sum of their lengths (slot npat of both is zeroed for the scans' totals).  Emitting
-// (kEmit = true; cnt_leaf / cnt_occ now hold the exclusive scans, the second being the call's
-// d_out_offs): leaf l, in traversal order from the pattern's first leaf, gets leaf_sp[l] (its
-// first row: a plain locate record, bit 63 clear), leaf_off[l] (its offset in the output) and
-// leaf_dist[l]; the thread after the last pattern writes the closing leaf_off[nleaf] = total.
-// A lane never writes at or past its pattern's leaf end, whatever the second traversal does
-// (LeafSink::leaf).  The leaves are then the "patterns" of launch_locate_walk.  An empty
-// pattern has no leaf (fm_index.cpp:109), nor has any pattern over an empty text.
-template <class E, int K, bool kEmit>
-__global__ __launch_bounds__(kBlk) void k_locate_mm(DevIndex ix, const uint8_t* __restrict__ pats,
-                                                    const uint64_t* __restrict__ offs, uint64_t npat,
-                                                    uint32_t k, uint64_t fixed_m, uint64_t* cnt_leaf,
-                                                    uint64_t* cnt_occ, uint64_t* __restrict__ leaf_sp,
-                                                    uint64_t* __restrict__ leaf_off,
-                                                    uint8_t* __restrict__ leaf_dist, uint64_t nleaf,
-                                                    uint64_t total) {
-  __shared__ NodeTable T;
-  __shared__ SymList L;
-  load_table(T, ix.table);
-  __syncthreads();
-  list_symbols(L, T);
-  const uint64_t q = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-  if (q > npat) return;
-  if (q == npat) {
-    if (kEmit) leaf_off[nleaf] = total;
-    else cnt_leaf[q] = cnt_occ[q] = 0;  // scan slots for the totals
-    return;
-  }
-  const uint64_t o0 = offs ? offs[q] : q * fixed_m, m = offs ? offs[q + 1] - o0 : fixed_m;
-  LeafSink sink;
-  sink.nleaf = kEmit ? cnt_leaf[q] : 0;
-  sink.nocc = kEmit ? cnt_occ[q] : 0;
-  sink.end = kEmit ? cnt_leaf[q + 1] : 0;
-  sink.leaf_sp = kEmit ? leaf_sp : nullptr;
-  sink.leaf_off = leaf_off;
-  sink.leaf_dist = leaf_dist;
-  if (m != 0 && ix.n != 0) mm_leaves<E, 0, K>(ix, T, L, pats + o0, m, k, m, 0, ix.n, sink);
-  if (!kEmit) {
-    cnt_leaf[q] = sink.nleaf;
-    cnt_occ[q] = sink.nocc;
-  }
-}
-
-// Best-stratum locate (cs_fm_locate_best_mismatch_device): round K of
-// launch_best_locate_mm_size / _emit, one pattern per lane; k_best_mm's rounds with
-// k_locate_mm's two passes.  The traversal is mm_leaves<E, 0, K> with kmax = K (K = 0: mm_rest,
-// no symbol list).  A pattern of round K has no hit below K, so its shallower subtrees die
-// where they died before and every leaf the sink sees is a non-empty one at depth K: exactly
-// stratum K, in the order k_locate_mm at the same bound visits those leaves.
-// Sizing (kEmit = false): round 0 runs over every pattern, round K >= 1 over the pending list
-// list_in[0 .. *len_in).  A lane with occurrences (in round 0 also an empty pattern over a
-// non-empty text, with no leaf) writes best_dist[q] = K, cnt_leaf[q], cnt_occ[q] and appends q
-// to the resolved list res at *res_len, a cursor shared by all rounds (the launch records it
-// after each round, so round K's patterns are one slice of res).  A lane without a hit appends
-// q to list_out or, in the last round, writes (CS_MM_NONE, 0, 0).  So every pattern's three
-// values are written exactly once over the rounds.  Both appends are k_best_mm's: one ballot
-// and one atomicAdd per wave, the lanes scatter by their prefix popcount.  A list's order
-// therefore depends on which wave's atomicAdd lands first; the result does not, since every
-// output is indexed by q.  The grid covers npat; a block whose first entry is at or past the
-// list's length returns before it stages anything, a block-uniform test ahead of every barrier.
-// Emitting (kEmit = true): over round K's resolved slice list_in[0 .. nlist) (nlist from the
-// host, the grid covers it; len_in and the append arguments are unused); cnt_leaf / cnt_occ
-// hold the exclusive scans (the second is d_out_offs) and leaf l of the pattern gets
-// leaf_sp[l], leaf_off[l] and a distance byte nobody reads.  A lane never writes at or past
-// its pattern's leaf end (LeafSink::leaf).  Nothing waits on another wave or block, and every
-// loop is bounded as mm_leaves' are.  list_out and res hold npat entries each; a pattern
-// enters at most one of them per round and res at most once.
-template <class E, int K, bool kEmit>
-__global__ __launch_bounds__(kBlk) void k_best_locate_mm(
-    DevIndex ix, const uint8_t* __restrict__ pats, const uint64_t* __restrict__ offs, uint64_t npat,
-    uint64_t fixed_m, bool last, const uint64_t* __restrict__ list_in,
-    const unsigned long long* __restrict__ len_in, uint64_t nlist, uint64_t* __restrict__ list_out,
-    unsigned long long* len_out, uint64_t* __restrict__ res, unsigned long long* res_len,
-    uint8_t* __restrict__ best_dist, uint64_t* cnt_leaf, uint64_t* cnt_occ,
-    uint64_t* __restrict__ leaf_sp, uint64_t* __restrict__ leaf_off, uint8_t* __restrict__ leaf_dist) {
-  if constexpr (!kEmit) {
-    nlist = npat;
-    if constexpr (K > 0) {
-      nlist = *len_in;
-      if (blockIdx.x * (uint64_t)blockDim.x >= nlist) return;
-    }
-  }
-  __shared__ NodeTable T;
-  __shared__ SymList L;
-  load_table(T, ix.table);
-  __syncthreads();
-  if constexpr (K > 0) list_symbols(L, T);
-  const uint64_t e = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-  // (no early return for the lanes past the list: the appends below are per wave)
-  uint64_t q = 0;
-  bool hit = false, miss = false;
-  if (e < nlist) {
-    if constexpr (K > 0 || kEmit) q = list_in[e];
-    else q = e;
-    const uint64_t o0 = offs ? offs[q] : q * fixed_m, m = offs ? offs[q + 1] - o0 : fixed_m;
-    LeafSink sink;
-    sink.nleaf = kEmit ? cnt_leaf[q] : 0;
-    sink.nocc = kEmit ? cnt_occ[q] : 0;
-    sink.end = kEmit ? cnt_leaf[q + 1] : 0;
-    sink.leaf_sp = kEmit ? leaf_sp : nullptr;
-    sink.leaf_off = leaf_off;
-    sink.leaf_dist = leaf_dist;
-    if (m != 0 && ix.n != 0) {
-      if constexpr (K == 0) mm_rest<E>(ix, T, pats + o0, m, 0, m, 0, ix.n, sink);
-      else mm_leaves<E, 0, K>(ix, T, L, pats + o0, m, (uint32_t)K, m, 0, ix.n, sink);
-    }
-    if constexpr (!kEmit) {
-      hit = sink.nocc != 0 || (K == 0 && m == 0 && ix.n != 0);  // fm_index.cpp:80
-      miss = !hit && !last;
-      if (!miss) {
-        best_dist[q] = hit ? (uint8_t)K : (uint8_t)CS_MM_NONE;
-        cnt_leaf[q] = sink.nleaf;
-        cnt_occ[q] = sink.nocc;
-      }
-    }
-  }
-  if constexpr (!kEmit) {
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t below = (1ull << lane) - 1ull;
-    const uint64_t bal_hit = __ballot(hit);
-    if (bal_hit) {  // wave-uniform
-      const uint32_t lead = (uint32_t)__ffsll((unsigned long long)bal_hit) - 1u;
-      unsigned long long base = 0;
-      if (lane == lead) base = atomicAdd(res_len, (unsigned long long)__popcll(bal_hit));
-      base = __shfl(base, (int)lead);
-      if (hit) res[base + (uint32_t)__popcll(bal_hit & below)] = q;
-    }
-    const uint64_t bal = __ballot(miss);
-    if (bal) {  // wave-uniform
-      const uint32_t lead = (uint32_t)__ffsll((unsigned long long)bal) - 1u;
-      unsigned long long base = 0;
-      if (lane == lead) base = atomicAdd(len_out, (unsigned long long)__popcll(bal));
-      base = __shfl(base, (int)lead);
-      if (miss) list_out[base + (uint32_t)__popcll(bal & below)] = q;
-    }
-  }
-}
-
-// d_out_dist[leaf_off[l] .. leaf_off[l + 1]) = leaf_dist[l].  A lane fills a leaf of at most
-// kLocSmall occurrences; the block's wider leaves (a 1-mer's holds n / 4 rows) are listed in
-// LDS and filled by the whole block, one after the other.
-__global__ __launch_bounds__(kBlk) void k_expand_dist(const uint64_t* __restrict__ leaf_off,
-                                                      const uint8_t* __restrict__ leaf_dist,
-                                                      uint64_t nleaf, uint8_t* __restrict__ out) {
-  __shared__ uint32_t s_wide[kBlk];
-  __shared__ uint32_t s_n;
-  if (threadIdx.x == 0) s_n = 0;
-  __syncthreads();
-  const uint64_t l0 = blockIdx.x * (uint64_t)blockDim.x, l = l0 + threadIdx.x;
-  if (l < nleaf) {
-    const uint64_t a = leaf_off[l], b = leaf_off[l + 1];
-    if (b - a <= kLocSmall) {
-      const uint8_t d = leaf_dist[l];
-      for (uint64_t i = a; i < b; ++i) out[i] = d;
-    } else {
-      s_wide[atomicAdd(&s_n, 1u)] = threadIdx.x;
-    }
-  }
-  __syncthreads();
-  const uint32_t nw = s_n;  // <= kBlk
-  for (uint32_t e = 0; e < nw; ++e) {
-    const uint64_t w = l0 + s_wide[e], a = leaf_off[w], b = leaf_off[w + 1];
-    const uint8_t d = leaf_dist[w];
-    for (uint64_t i = a + threadIdx.x; i < b; i += blockDim.x) out[i] = d;
-  }
-}
-
 // The batch count over occurrence lines with left contexts, the C4/C5 shape: a
 // pattern whose last k = ptab_k characters are in the prefix table and whose other
 // m - k <= kCtxQ characters are coded needs two dependent reads — its table entry,
@@ -4003,9 +3722,6 @@ inline bool count_nobar(uint32_t flags) { return !(flags & CS_QT_BARRIER); }
 // pattern per lane) instead of the staged k_count_qctx
 inline bool qctx_staged(uint32_t flags) { return !(flags & CS_QT_QCTX_UNSTAGED); }
 
-// the call's flags with the handle's tuning defaults
-inline uint32_t call_flags(const cs_fm_index* h, uint32_t flags) { return flags | h->tune; }
-
 // The call's long-pattern lists (LongList): the counters' header (kListHdrBytes, zero between
 // calls), slot lists of the staged kernel (list / cnt, unless `direct`) and of k_count_long /
 // k_locate_long for the general search (list2 / cnt2), offsets inside the slots' regions (u16; list2 u32 with the chain);
@@ -4277,234 +3993,6 @@ cs_status launch_count_ex(const cs_fm_index* h, const uint8_t* d_pats, const uin
   }
   FMX_HIP(hipGetLastError());
   return CS_OK;
-}
-
-cs_status launch_count_mm(const cs_fm_index* h, const uint8_t* d_pats, const uint64_t* d_offs,
-                          uint64_t npat, uint32_t k, uint64_t* d_hist, uint32_t flags, hipStream_t st,
-                          uint64_t fixed_m) {
-  if (!npat) return CS_OK;
-  const DevIndex ix = query_dev(h, call_flags(h, flags));
-  const unsigned g = grid_for(npat, kBlk, 0xFFFFFFFFu);
-  with_engine(h->line_fmt, [&](auto engine) {
-    with_int<2, 3, 1>((int)k, [&](auto K) {  // (k = 0 takes K = 1)
-      using E = typename decltype(engine)::type;
-      k_count_mm<E, K><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, k, d_hist, fixed_m);
-    });
-  });
-  FMX_HIP(hipGetLastError());
-  return CS_OK;
-}
-
-cs_status launch_best_mm(const cs_fm_index* h, const uint8_t* d_pats, const uint64_t* d_offs,
-                         uint64_t npat, uint32_t k, uint8_t* d_best_dist, uint64_t* d_best_count,
-                         uint32_t flags, hipStream_t st, uint64_t fixed_m) {
-  if (!npat) return CS_OK;
-  // round r reads list r - 1 and appends to list r; the lists alternate between the two
-  // halves of `lists`, len[r] is list r's length
-  StreamBuf lists, len;
-  if (k) {
-    FMX_HIP(lists.alloc(2 * npat * 8, st));
-    FMX_HIP(len.alloc(CS_MM_MAX * 8, st));
-    FMX_HIP(hipMemsetAsync(len.p, 0, CS_MM_MAX * 8, st));
-  }
-  const DevIndex ix = query_dev(h, call_flags(h, flags));
-  // a round's list length is known on the device only: every round's grid covers npat
-  const unsigned g = grid_for(npat, kBlk, 0xFFFFFFFFu);
-  with_engine(h->line_fmt, [&](auto engine) {
-    using E = typename decltype(engine)::type;
-    for (uint32_t r = 0; r <= k; ++r) {
-      uint64_t* const in = r ? lists.as<uint64_t>() + ((r - 1) & 1) * npat : nullptr;
-      uint64_t* const out = r < k ? lists.as<uint64_t>() + (r & 1) * npat : nullptr;
-      unsigned long long* const ln = len.as<unsigned long long>();
-      with_int<0, 1, 2, 3>((int)r, [&](auto K) {
-        k_best_mm<E, K><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, fixed_m, /*last*/ r == k, in,
-                                            r ? ln + (r - 1) : nullptr, out, r < k ? ln + r : nullptr,
-                                            d_best_dist, d_best_count);
-      });
-    }
-  });
-  FMX_HIP(hipGetLastError());
-  return CS_OK;
-}
-
-cs_status launch_locate_mm_size(const cs_fm_index* h, const uint8_t* d_pats, const uint64_t* d_offs,
-                                uint64_t npat, uint32_t k, uint64_t fixed_m, uint64_t* d_out_offs,
-                                uint32_t flags, hipStream_t st, MmLeafPlan& plan, hipEvent_t* ev) {
-  StreamBuf cnt_leaf, cnt_occ, tmp;
-  FMX_HIP(cnt_leaf.alloc((npat + 1) * 8, st));
-  FMX_HIP(cnt_occ.alloc((npat + 1) * 8, st));
-  FMX_HIP(plan.leaf_base.alloc((npat + 1) * 8, st));
-  const DevIndex ix = query_dev(h, call_flags(h, flags));
-  const unsigned g = grid_for(npat + 1, kBlk, 0xFFFFFFFFu);
-  if (ev) FMX_HIP(hipEventRecord(ev[0], st));
-  with_engine(h->line_fmt, [&](auto engine) {
-    with_int<2, 3, 1>((int)k, [&](auto K) {  // (k = 0 takes K = 1)
-      using E = typename decltype(engine)::type;
-      k_locate_mm<E, K, false><<<g, kBlk, 0, st>>>(ix, d_pats, d_offs, npat, k, fixed_m,
-                                                   cnt_leaf.as<uint64_t>(), cnt_occ.as<uint64_t>(),
-                                                   nullptr, nullptr, nullptr, 0, 0);
-    });
-  });
-  FMX_HIP(hipGetLastError());
-  if (ev) FMX_HIP(hipEventRecord(ev[1], st));
-  // the two exclusive scans (one temporary serves both: same type, same length)
-  size_t tb = 0;
-  FMX_HIP(rocprim::exclusive_scan(nullptr, tb, cnt_occ.as<uint64_t>(), d_out_offs, (uint64_t)0,
-                                  npat + 1, rocprim::plus<uint64_t>(), st));
-  FMX_HIP(tmp.alloc(tb, st));
-  FMX_HIP(rocprim::exclusive_scan(tmp.p, tb, cnt_occ.as<uint64_t>(), d_out_offs, (uint64_t)0,
-                                  npat + 1, rocprim::plus<uint64_t>(), st));
-  FMX_HIP(rocprim::exclusive_scan(tmp.p, tb, cnt_leaf.as<uint64_t>(), plan.leaf_base.as<uint64_t>(),
-                                  (uint64_t)0, npat + 1, rocprim::plus<uint64_t>(), st));
-  FMX_HIP(hipMemcpyAsync(&plan.total, d_out_offs + npat, 8, hipMemcpyDeviceToHost, st));
-  FMX_HIP(hipMemcpyAsync(&plan.nleaf, plan.leaf_base.as<uint64_t>() + npat, 8, hipMemcpyDeviceToHost, st));
-  if (ev) FMX_HIP(hipEventRecord(ev[2], st));
-  FMX_HIP(hipStreamSynchronize(st));
-  return CS_OK;
-}
-
-cs_status launch_locate_mm_emit(const cs_fm_index* h, const uint8_t* d_pats, const uint64_t* d_offs,
-                                uint64_t npat, uint32_t k, uint64_t fixed_m,
-                                const uint64_t* d_out_offs, const MmLeafPlan& plan,
-                                uint64_t* d_out_pos, uint8_t* d_out_dist, uint32_t flags,
-                                hipStream_t st, hipEvent_t* ev) {
-  const uint64_t nleaf = plan.nleaf, total = plan.total;
-  StreamBuf leaf_sp, leaf_off, leaf_dist, err;
-  FMX_HIP(leaf_sp.alloc(nleaf * 8, st));
-  FMX_HIP(leaf_off.alloc((nleaf + 1) * 8, st));
-  FMX_HIP(leaf_dist.alloc(nleaf, st));
-  FMX_HIP(err.alloc(8, st));
-  FMX_HIP(hipMemsetAsync(err.p, 0xFF, 8, st));
-  const DevIndex ix = query_dev(h, call_flags(h, flags));
-  const unsigned g = grid_for(npat + 1, kBlk, 0xFFFFFFFFu);
-  with_engine(h->line_fmt, [&](auto engine) {
-    with_int<2, 3, 1>((int)k, [&](auto K) {
-      using E = typename decltype(engine)::type;
-      k_locate_mm<E, K, true><<<g, kBlk, 0, st>>>(
-          ix, d_pats, d_offs, npat, k, fixed_m, plan.leaf_base.as<uint64_t>(),
-          const_cast<uint64_t*>(d_out_offs), leaf_sp.as<uint64_t>(), leaf_off.as<uint64_t>(),
-          leaf_dist.as<uint8_t>(), nleaf, total);
-    });
-  });
-  FMX_HIP(hipGetLastError());
-  if (ev) FMX_HIP(hipEventRecord(ev[3], st));
-  // the positions: the exact locate's phase 2 with the leaves as its patterns
-  unsigned long long* e = err.as<unsigned long long>();
-  cs_status s = launch_locate_walk(h, leaf_sp.as<uint64_t>(), leaf_off.as<uint64_t>(), nleaf, total,
-                                   d_out_pos, st, e, flags);
-  if (s != CS_OK) return s;
-  if (ev) FMX_HIP(hipEventRecord(ev[4], st));
-  if (nleaf) {
-    k_expand_dist<<<grid_for(nleaf, kBlk, 0xFFFFFFFFu), kBlk, 0, st>>>(
-        leaf_off.as<uint64_t>(), leaf_dist.as<uint8_t>(), nleaf, d_out_dist);
-    FMX_HIP(hipGetLastError());
-  }
-  if (ev) FMX_HIP(hipEventRecord(ev[5], st));
-  return check_locate_error(h, e, st);
-}
-
-cs_status launch_best_locate_mm_size(const cs_fm_index* h, const uint8_t* d_pats,
-                                     const uint64_t* d_offs, uint64_t npat, uint32_t k,
-                                     uint64_t fixed_m, uint8_t* d_best_dist, uint64_t* d_out_offs,
-                                     uint32_t flags, hipStream_t st, BestLeafPlan& plan) {
-  // control words: [0, CS_MM_MAX) the pending lists' lengths (round r reads list r - 1 and
-  // appends to list r, the lists alternate between the halves of `lists`), then the resolved
-  // list's cursor, and what the host reads back in one copy: bound[0 .. CS_MM_MAX + 2) (those
-  // past k + 1 stay 0 and are not used), total, nleaf
-  constexpr uint32_t kCur = CS_MM_MAX, kBound = kCur + 1, kTotal = kBound + CS_MM_MAX + 2,
-                     kWords = kTotal + 2;
-  StreamBuf cnt_leaf, cnt_occ, lists, ctl, tmp;
-  FMX_HIP(cnt_leaf.alloc((npat + 1) * 8, st));
-  FMX_HIP(cnt_occ.alloc((npat + 1) * 8, st));
-  FMX_HIP(plan.leaf_base.alloc((npat + 1) * 8, st));
-  FMX_HIP(plan.res.alloc(npat * 8, st));
-  if (k) FMX_HIP(lists.alloc(2 * npat * 8, st));
-  FMX_HIP(ctl.alloc(kWords * 8, st));
-  FMX_HIP(hipMemsetAsync(ctl.p, 0, kWords * 8, st));
-  // scan slots for the totals
-  FMX_HIP(hipMemsetAsync(cnt_leaf.as<uint64_t>() + npat, 0, 8, st));
-  FMX_HIP(hipMemsetAsync(cnt_occ.as<uint64_t>() + npat, 0, 8, st));
-  const DevIndex ix = query_dev(h, call_flags(h, flags));
-  unsigned long long* const w = ctl.as<unsigned long long>();
-  // a round's list length is known on the device only: every round's grid covers npat
-  const unsigned g = grid_for(npat, kBlk, 0xFFFFFFFFu);
-  hipError_t err = hipSuccess;
-  with_engine(h->line_fmt, [&](auto engine) {
-    using E = typename decltype(engine)::type;
-    for (uint32_t r = 0; r <= k && err == hipSuccess; ++r) {
-      uint64_t* const in = r ? lists.as<uint64_t>() + ((r - 1) & 1) * npat : nullptr;
-      uint64_t* const out = r < k ? lists.as<uint64_t>() + (r & 1) * npat : nullptr;
-      with_int<0, 1, 2, 3>((int)r, [&](auto K) {
-        k_best_locate_mm<E, K, false><<<g, kBlk, 0, st>>>(
-            ix, d_pats, d_offs, npat, fixed_m, /*last*/ r == k, in, r ? w + (r - 1) : nullptr, 0, out,
-            r < k ? w + r : nullptr, plan.res.as<uint64_t>(), w + kCur, d_best_dist,
-            cnt_leaf.as<uint64_t>(), cnt_occ.as<uint64_t>(), nullptr, nullptr, nullptr);
-      });
-      // round r's patterns are res[bound[r] .. bound[r + 1])
-      err = hipMemcpyAsync(w + kBound + r + 1, w + kCur, 8, hipMemcpyDeviceToDevice, st);
-    }
-  });
-  FMX_HIP(err);
-  FMX_HIP(hipGetLastError());
-  // the two exclusive scans (one temporary serves both: same type, same length)
-  size_t tb = 0;
-  FMX_HIP(rocprim::exclusive_scan(nullptr, tb, cnt_occ.as<uint64_t>(), d_out_offs, (uint64_t)0,
-                                  npat + 1, rocprim::plus<uint64_t>(), st));
-  FMX_HIP(tmp.alloc(tb, st));
-  FMX_HIP(rocprim::exclusive_scan(tmp.p, tb, cnt_occ.as<uint64_t>(), d_out_offs, (uint64_t)0,
-                                  npat + 1, rocprim::plus<uint64_t>(), st));
-  FMX_HIP(rocprim::exclusive_scan(tmp.p, tb, cnt_leaf.as<uint64_t>(), plan.leaf_base.as<uint64_t>(),
-                                  (uint64_t)0, npat + 1, rocprim::plus<uint64_t>(), st));
-  // one read-back: the bounds and the two totals
-  FMX_HIP(hipMemcpyAsync(w + kTotal, d_out_offs + npat, 8, hipMemcpyDeviceToDevice, st));
-  FMX_HIP(hipMemcpyAsync(w + kTotal + 1, plan.leaf_base.as<uint64_t>() + npat, 8,
-                         hipMemcpyDeviceToDevice, st));
-  uint64_t back[CS_MM_MAX + 4];
-  FMX_HIP(hipMemcpyAsync(back, w + kBound, sizeof back, hipMemcpyDeviceToHost, st));
-  FMX_HIP(hipStreamSynchronize(st));
-  for (uint32_t r = 0; r < CS_MM_MAX + 2; ++r) plan.bound[r] = back[r];
-  plan.total = back[CS_MM_MAX + 2];
-  plan.nleaf = back[CS_MM_MAX + 3];
-  return CS_OK;
-}
-
-cs_status launch_best_locate_mm_emit(const cs_fm_index* h, const uint8_t* d_pats,
-                                     const uint64_t* d_offs, uint64_t npat, uint32_t k,
-                                     uint64_t fixed_m, const uint64_t* d_out_offs,
-                                     const BestLeafPlan& plan, uint64_t* d_out_pos, uint32_t flags,
-                                     hipStream_t st) {
-  const uint64_t nleaf = plan.nleaf, total = plan.total;
-  StreamBuf leaf_sp, leaf_off, leaf_dist, err;
-  FMX_HIP(leaf_sp.alloc(nleaf * 8, st));
-  FMX_HIP(leaf_off.alloc((nleaf + 1) * 8, st));
-  FMX_HIP(leaf_dist.alloc(nleaf, st));  // LeafSink's distance per leaf: all K in round K, unread
-  FMX_HIP(err.alloc(8, st));
-  FMX_HIP(hipMemsetAsync(err.p, 0xFF, 8, st));
-  const DevIndex ix = query_dev(h, call_flags(h, flags));
-  with_engine(h->line_fmt, [&](auto engine) {
-    using E = typename decltype(engine)::type;
-    for (uint32_t r = 0; r <= k; ++r) {
-      const uint64_t nres = plan.bound[r + 1] - plan.bound[r];
-      if (!nres) continue;
-      with_int<0, 1, 2, 3>((int)r, [&](auto K) {
-        k_best_locate_mm<E, K, true><<<grid_for(nres, kBlk, 0xFFFFFFFFu), kBlk, 0, st>>>(
-            ix, d_pats, d_offs, npat, fixed_m, false, plan.res.as<uint64_t>() + plan.bound[r], nullptr,
-            nres, nullptr, nullptr, nullptr, nullptr, nullptr, plan.leaf_base.as<uint64_t>(),
-            const_cast<uint64_t*>(d_out_offs), leaf_sp.as<uint64_t>(), leaf_off.as<uint64_t>(),
-            leaf_dist.as<uint8_t>());
-      });
-    }
-  });
-  FMX_HIP(hipGetLastError());
-  // the closing leaf_off[nleaf] = total
-  FMX_HIP(hipMemcpyAsync(leaf_off.as<uint64_t>() + nleaf, d_out_offs + npat, 8, hipMemcpyDeviceToDevice, st));
-  // the positions: the exact locate's phase 2 with the leaves as its patterns; the leaves are
-  // in pattern order, so the output is in batch order
-  unsigned long long* e = err.as<unsigned long long>();
-  cs_status s = launch_locate_walk(h, leaf_sp.as<uint64_t>(), leaf_off.as<uint64_t>(), nleaf, total,
-                                   d_out_pos, st, e, flags);
-  if (s != CS_OK) return s;
-  return check_locate_error(h, e, st);
 }
 
 cs_status launch_count_one(const cs_fm_index* h, const OnePattern& p, uint64_t* out_host,

@@ -1,5 +1,5 @@
-// fm_search.hpp — device-side search helpers shared by the query kernels (fm_query.hip)
-// and the index-structure builders (fm_structs.hip): the node table in LDS, one
+// fm_search.hpp — device-side search helpers shared by the query kernels (fm_query.hip,
+// fm_mismatch.hip) and the index-structure builders (fm_structs.hip): the node table in LDS, one
 // backward-search step per rank engine, the prefix-table / left-context / record
 // lookups and the search loops the kernels are built from, plus the dispatch helpers
 // (with_engine, with_walk_line, with_bool, with_int).  Everything sits in an anonymous
@@ -954,7 +954,7 @@ __device__ __forceinline__ uint64_t count_rest(const DevIndex& ix, const NodeTab
   return ep - sp;
 }
 
-// ---- count within k mismatches (k_count_mm; include/cs_fmindex_approx.h) ----
+// ---- search within k mismatches (fm_mismatch.hip; include/cs_fmindex_approx*.h) ----
 // The substitute alphabet: the symbols present in the text (C[c] < C[c+1]), ascending, listed
 // once per block.  Every thread of a kBlk block calls list_symbols after the node table is
 // staged; it ends with a barrier.
