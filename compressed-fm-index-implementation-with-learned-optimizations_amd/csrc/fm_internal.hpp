@@ -267,7 +267,8 @@ class BuildOptScope {
 // offending token in err for a malformed pair or a name no builder reads
 bool parse_build_options(const char* text, BuildOptions& o, std::string& err);
 
-// Query launches (fm_query.hip; the mismatch family's in fm_mismatch.hip).
+// Query launches (fm_query.hip; locate's phase 2 in fm_walk.hip, the mismatch family's in
+// fm_mismatch.hip).
 // the call's flags with the handle's tuning defaults
 inline uint32_t call_flags(const cs_fm_index* h, uint32_t flags) { return flags | h->tune; }
 // the index as one query sees it under the caller's query flags (fm_query.hip)

@@ -4,7 +4,7 @@
 // fm_search.hpp (mm_frame for the histograms, mm_leaves for the leaves) under four kernels, one
 // pattern per lane, templates over the rank engine as the kernels of fm_query.hip; the helpers
 // below are what the four share.  The
-// positions of the locates come from the exact locate's walk (launch_locate_walk, fm_query.hip)
+// positions of the locates come from the exact locate's walk (launch_locate_walk, fm_walk.hip)
 // with the search's leaves as its patterns.
 #include "fm_search.hpp"
 

@@ -1,6 +1,6 @@
 // fm_query.hip — the hot path: batched backward search (FMIndex::count,
-// src/api/fm_index.cpp:79-101) and the LF/SSA walk of FMIndex::locate
-// (src/api/fm_index.cpp:107-157), as hand-written CDNA4 kernels.
+// src/api/fm_index.cpp:79-101) and the search of FMIndex::locate
+// (src/api/fm_index.cpp:107-124), as hand-written CDNA4 kernels.
 //
 // Every kernel is a template over a rank ENGINE (occ(c, i) for a search step, and
 // LF with the BWT symbol), dispatched on the index's format (with_engine, fm_search.hpp):
@@ -18,12 +18,10 @@
 // the reference returns 0.
 //
 // locate: (1) the same search writes sp and min(count, limit); (2) exclusive scan ->
-// CSR offsets; (3) rows expanded in row order (fm_index.cpp:125); (4) a persistent
-// walk kernel: each block owns a contiguous slice of rows, its lanes pull rows from
-// an LDS counter and cycle fetch -> walk -> sample with one dependent load per loop
-// iteration.  With walk lines (fm_device.hpp WalkLine) one 32-B read per step gives
-// the symbol, its occ and the sample mark; no separate BWT array is kept.
-#include "fm_search.hpp"
+// CSR offsets; then phase 2, the positions of the reported rows (fm_walk.hip).  The
+// one-call locate (below) does the three in one call; its walks, and those of
+// k_count_long's walk-verify forms, are fm_walk.hpp's.
+#include "fm_walk.hpp"
 
 namespace fmx {
 namespace {
@@ -181,15 +179,7 @@ __device__ __forceinline__ void general_rest(const DevIndex& ix, const NodeTable
 // each, then the mark's sample) instead of SA[row], in (1) for a pattern's only position
 // and in (3) / k_locate_emit_wide for the rest (kPos: 0 the full SA, 1 WalkLine, 2
 // WalkLineW).  Counts are u64 (cnt64) when the index is wide.
-// The one-call locate's outputs (offsets and positions) leave through non-temporal stores:
-// nothing on the device reads them again (C4 one call 0.853 -> 0.818 ms in an A/B on one
-// box; the search kernel's records and counts, which the emit kernel reads back, measured
-// the same either way: profiles/r03/ab_nt_locate.jsonl)
-template <class T>
-__device__ __forceinline__ void st_out(T* p, T v) {
-  __builtin_nontemporal_store(v, p);
-}
-
+// The outputs (offsets and positions) leave through non-temporal stores (st_out).
 struct OnePass {
   uint32_t* cnt = nullptr;               // (1) -> (3): min(count, limit) per pattern (narrow),
                                          // unless its record is a stashed position (count 1)
@@ -206,7 +196,7 @@ struct OnePass {
   uint64_t wide_cap = 0;
   uint32_t defer = 0;  // locate records: a pattern its record does not answer -> k_locate_list
   // walk-line indexes (kPos 1 / 2): the positions of patterns with 2..kLocSmall rows, as
-  // (output index, row | adj << 56) pairs for k_locate_walks — one lane per position, so no
+  // (output index, row | adj << kWalkAdjShift) pairs for k_locate_walks — one lane per position, so no
   // emit wave waits on a lane's chain of walks — kLocTile slots per tile (tile t's at
   // t kLocTile, their number in wcnt[t]: no global counter); past them the emit walks them
   uint64_t* walks = nullptr;
@@ -217,7 +207,6 @@ struct OnePass {
 };
 constexpr uint32_t kScanBlock = 1024;     // tiles per block of k_scan_chained
 constexpr uint32_t kScanMaxBlocks = 1024; // (its look-back: one predecessor per thread)
-constexpr uint32_t kWalkAdjShift56 = 56;
 __device__ __forceinline__ void onepass_zero(const OnePass& op) {
   // the call's wide-range counter and the chained scan's flags and ticket (no memset launch;
   // stream order makes the stores visible to the kernels after this one)
@@ -230,38 +219,6 @@ __device__ __forceinline__ void onepass_zero(const OnePass& op) {
 // Tiles of the one-call locate's scan (k_count_ctx kOne with U = 2 patterns per lane)
 constexpr uint64_t kLocTile = 2 * kBlk;
 static_assert(kLocTile == kLongRegion, "a tile is a region: one block's patterns");
-
-// the text position of BWT row `row` by the short walk, and the same for U rows walked in
-// lockstep (their line reads in flight together) — defined with the walks below
-template <class W>
-__device__ __forceinline__ uint64_t walk_position(const DevIndex& ix, const NodeTable& T, uint64_t row);
-template <class W>
-__device__ __forceinline__ uint64_t walk_position_steps(const DevIndex& ix, const NodeTable& T, uint64_t row,
-                                                        uint64_t& steps);
-template <class W, int U>
-__device__ __forceinline__ void walk_positions(const DevIndex& ix, const NodeTable& T, uint64_t* pos,
-                                               bool* act);
-// the constants an LF step of a walk reads from the node table, held in registers by a
-// barrier-free kernel whose table is the global one (a walk step through the caches waits on
-// two more dependent loads: round 5, C5's one-call search 1.56 -> 1.70 ms that way)
-struct WalkK {
-  uint64_t C[4];     // C[] of each occurrence code's symbol
-  uint32_t nexc;     // rare rows
-  uint64_t exc_row0; // the rare row when there is one (C5's terminator), and C[] of its symbol
-  uint64_t exc_c0;
-};
-__device__ __forceinline__ WalkK walk_consts(const NodeTable& T) {
-  WalkK k;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) k.C[c] = T.C[T.occ_sym[c]];
-  k.nexc = T.exc_n;
-  k.exc_row0 = k.nexc ? T.exc_row[0] : 0;
-  k.exc_c0 = k.nexc ? T.C[T.exc_sym[0]] : 0;
-  return k;
-}
-template <class W, int U>
-__device__ __forceinline__ void walk_positions_k(const DevIndex& ix, const NodeTable& T, const WalkK& K,
-                                                 uint64_t* pos, bool* act);
 
 // position of BWT row `row` for the one-call locate: SA[row] (kPos 0) or the short walk
 template <int kPos>
@@ -441,29 +398,21 @@ __global__ __launch_bounds__(1024) void k_scan_tiles(uint64_t* __restrict__ tile
   if (t == 0) *total_out = s_carry;
 }
 
-// the positions of c <= kLocSmall rows — rows r0 + i, or r0 + the set bits of rel (a context
-// window) — minus adj (mod n), to out: SA reads kEmitRows at a time, in flight together
+// the positions of a record's first c <= kLocSmall reported rows, minus the window's adj
+// (mod n), to out: SA reads kEmitRows at a time, in flight together
 // (the walk-line forms list their rows instead: emit_walk_lines)
 constexpr int kEmitRows = 4;
 template <int kPos>
 __device__ __forceinline__ void emit_rows(const DevIndex& ix, const NodeTable& T, const OnePass& op,
-                                          uint64_t* __restrict__ out, uint64_t c, uint64_t r0, uint32_t rel,
-                                          uint64_t adj) {
-  const uint64_t n = ix.n;
+                                          uint64_t* __restrict__ out, uint64_t c, LocRows rows) {
+  const uint64_t n = ix.n, adj = rows.adj;
   for (uint64_t i = 0; i < c; i += kEmitRows) {
     uint64_t row[kEmitRows];
     bool act[kEmitRows];
 #pragma unroll
     for (int u = 0; u < kEmitRows; ++u) {
       act[u] = i + u < c;
-      row[u] = 0;
-      if (!act[u]) continue;
-      if (rel) {
-        row[u] = r0 + (uint32_t)__ffs(rel) - 1u;
-        rel &= rel - 1u;
-      } else {
-        row[u] = r0 + i + u;
-      }
+      row[u] = act[u] ? rows.next() : 0;
     }
     static_assert(kPos == 0, "walk-line indexes list their rows (emit_walk_lines)");
 #pragma unroll
@@ -577,18 +526,12 @@ __device__ __forceinline__ void emit_walk_lines(const DevIndex& ix, NodeTable& T
     const uint64_t a = base + mine[j], s = kr[j], c = nl[j];
     const bool fits = at + c <= kLocTile;
     fb |= (uint32_t)!fits << j;
-    uint64_t r0 = s, adj = 0;
-    uint32_t rel = 0;
-    if (s & kLocCtx) loc_window(s, r0, adj, rel);
+    LocRows rows = LocRows::of(s);
     for (uint64_t i = 0; i < c; ++i, ++at) {
-      uint64_t row = r0 + i;
-      if (rel) {
-        row = r0 + (uint32_t)__ffs(rel) - 1u;
-        rel &= rel - 1u;
-      }
+      const uint64_t row = rows.next();
       if (at >= kLocTile) continue;
       slots[2 * at] = fits ? a + i : ~0ull;  // (a void slot: k_locate_walks skips it)
-      slots[2 * at + 1] = row | (adj << kWalkAdjShift56);
+      slots[2 * at + 1] = row | (rows.adj << kWalkAdjShift);
     }
   }
   if (__syncthreads_or(fb != 0)) {
@@ -597,17 +540,11 @@ __device__ __forceinline__ void emit_walk_lines(const DevIndex& ix, NodeTable& T
 #pragma unroll
     for (int j = 0; j < U; ++j) {
       if (!((fb >> j) & 1u)) continue;
-      const uint64_t a = base + mine[j], s = kr[j];
-      uint64_t r0 = s, adj = 0;
-      uint32_t rel = 0;
-      if (s & kLocCtx) loc_window(s, r0, adj, rel);
+      const uint64_t a = base + mine[j];
+      LocRows rows = LocRows::of(kr[j]);
+      const uint64_t adj = rows.adj;
       for (uint64_t i = 0; i < nl[j]; ++i) {
-        uint64_t row = r0 + i;
-        if (rel) {
-          row = r0 + (uint32_t)__ffs(rel) - 1u;
-          rel &= rel - 1u;
-        }
-        const uint64_t p = walk_position<W>(ix, T, row);
+        const uint64_t p = walk_position<W>(ix, T, rows.next());
         st_out(op.out_pos + a + i, p >= adj ? p - adj : p + n - adj);
       }
     }
@@ -664,8 +601,8 @@ __global__ __launch_bounds__(kBlk) void k_locate_walks(DevIndex ix, OnePass op, 
       idx[h] = ee < tot ? sl[0] : ~0ull;
       const uint64_t v = ee < tot ? sl[1] : 0;
       act[h] = idx[h] != ~0ull;
-      row[h] = v & ((1ull << kWalkAdjShift56) - 1);
-      adj[h] = v >> kWalkAdjShift56;
+      row[h] = v & kWalkRowMask;
+      adj[h] = v >> kWalkAdjShift;
     }
     bool w[2] = {act[0], act[1]};
     walk_positions<W, 2>(ix, T, row, w);
@@ -716,12 +653,9 @@ __global__ __launch_bounds__(kBlk) void k_locate_emit(DevIndex ix, uint64_t npat
       if (loc_stashed(s)) {  // kLocStash: the one position, read by the search kernel
         st_out(op.out_pos + a, s & (kLocStash - 1));
       } else if (s & kLocCtx) {  // a window k characters before the end (k_locate_sa)
-        uint64_t r0, adj;
-        uint32_t rel;
-        loc_window(s, r0, adj, rel);
-        emit_rows<kPos>(ix, T, op, op.out_pos + a, c, r0, rel, adj);
+        emit_rows<kPos>(ix, T, op, op.out_pos + a, c, LocRows::of(s));
       } else if (c <= kLocSmall) {
-        emit_rows<kPos>(ix, T, op, op.out_pos + a, c, s, 0u, 0);
+        emit_rows<kPos>(ix, T, op, op.out_pos + a, c, LocRows(s));
       } else {
         const unsigned long long e = atomicAdd(op.nwide, 1ull);
         if (e < op.wide_cap) {
@@ -2121,7 +2055,7 @@ __device__ __forceinline__ void count_long_one(const DevIndex& ix, const uint8_t
       if constexpr (kWalk != 0) {
         using WL = std::conditional_t<kWalk == 1, WalkLine, WalkLineW>;
         if constexpr (kBytes) {  // (the twin counts the walk's lines)
-          p = walk_position_steps<WL>(ix, *ix.table, base + i, wsteps);
+          p = walk_one<WL, false>(ix, *ix.table, base + i, wsteps);
         } else {
           uint64_t pos[1] = {base + i};
           bool act[1] = {true};
@@ -2969,561 +2903,6 @@ __global__ __launch_bounds__(kBlk) void k_locate_one_gen(DevIndex ix, const uint
   locate_split_store<U, 0>(ix, T, npat, blockIdx.x, q0, kc, kr, op);
 }
 
-}  // namespace
-
-// Phase 2 with the full suffix array, fused (no rows buffer): each pattern's rows come
-// from its record (as k_expand_rows) and go straight through SA: SA[row] - k (mod n) for
-// a window row k characters before the end, SA[row] otherwise.  A lane
-// takes a pattern of at most kLocSmall rows (every context window: <= kLocSpanBits);
-// wider plain ranges are listed for k_locate_sa_wide, a block per range.
-__global__ __launch_bounds__(kBlk) void k_locate_sa(const uint32_t* __restrict__ sa, uint64_t n,
-                                                    const uint64_t* __restrict__ sp,
-                                                    const uint64_t* __restrict__ offs, uint64_t npat,
-                                                    uint64_t* __restrict__ out,
-                                                    uint64_t* __restrict__ wide,
-                                                    unsigned long long* __restrict__ nwide) {
-  const uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t q = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; q < npat; q += gs) {
-    const uint64_t a = offs[q], c = offs[q + 1] - a, s = sp[q];
-    if (!c) continue;
-    if (s & kLocCtx) {
-      uint64_t r0, adj;
-      uint32_t rel;
-      loc_window(s, r0, adj, rel);
-      for (uint64_t j = 0; j < c; ++j) {
-        const uint32_t f = (uint32_t)__ffs(rel) - 1u;
-        const uint64_t p = load_sa(sa, r0 + f);
-        st_out(out + a + j, p >= adj ? p - adj : p + n - adj);
-        rel &= rel - 1u;
-      }
-    } else if (c <= kLocSmall) {
-      for (uint64_t j = 0; j < c; ++j) st_out(out + a + j, (uint64_t)sa[s + j]);
-    } else {
-      wide[atomicAdd(nwide, 1ull)] = q;
-    }
-  }
-}
-
-__global__ __launch_bounds__(kBlk) void k_locate_sa_wide(const uint32_t* __restrict__ sa,
-                                                         const uint64_t* __restrict__ sp,
-                                                         const uint64_t* __restrict__ offs,
-                                                         uint64_t* __restrict__ out,
-                                                         const uint64_t* __restrict__ wide,
-                                                         const unsigned long long* __restrict__ nwide) {
-  const uint64_t nw = *nwide;
-  for (uint64_t e = blockIdx.x; e < nw; e += gridDim.x) {
-    const uint64_t q = wide[e], a = offs[q], c = offs[q + 1] - a, s = sp[q];
-    for (uint64_t j = threadIdx.x; j < c; j += blockDim.x) st_out(out + a + j, (uint64_t)sa[s + j]);
-  }
-}
-
-namespace {  // (the two kernels above keep their external names)
-
-// The reported rows of pattern q in row order (fm_index.cpp:125): sp[q] + (j -
-// offs[q]) for a plain record, else the window's matching rows, tagged with k.
-__global__ void k_expand_rows(const uint64_t* __restrict__ sp, const uint64_t* __restrict__ offs,
-                              uint64_t npat, uint64_t* __restrict__ rows) {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t q = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; q < npat; q += stride) {
-    const uint64_t a = offs[q], b = offs[q + 1], s = sp[q];
-    if (s & kLocCtx) {
-      const uint64_t r0 = s & kLocRowMask, tag = ((s >> 60) & 7u) << kWalkAdjShift;
-      uint32_t rel = (uint32_t)(s >> 38) & ((1u << kLocSpanBits) - 1u);
-      for (uint64_t j = a; j < b; ++j) {
-        const uint32_t f = (uint32_t)__ffs(rel) - 1u;
-        rows[j] = (r0 + f) | tag;
-        rel &= rel - 1u;
-      }
-    } else {
-      for (uint64_t j = a; j < b; ++j) rows[j] = s + (j - a);
-    }
-  }
-}
-
-template <bool POW2>
-__device__ __forceinline__ bool is_sampled(const DevIndex& ix, uint64_t row) {
-  if (POW2) return (row & ((1ull << ix.stride_shift) - 1)) == 0;
-  return row % ix.stride == 0;
-}
-
-template <bool POW2>
-__device__ __forceinline__ uint64_t sample_index(const DevIndex& ix, uint64_t row) {
-  if (POW2) return row >> ix.stride_shift;
-  return row / ix.stride;
-}
-
-// Persistent LF walk (fm_index.cpp:125-153).  Block b owns rows [b*chunk, ...);
-// lanes pull rows from an LDS counter and cycle FETCH -> WALK -> SAMPLE as in
-// k_walk_lines below (the SSA read of a finishing lane does not add a round trip
-// to its wave's LF step).
-template <class E, bool POW2>
-__global__ __launch_bounds__(kBlk) void k_walk(DevIndex ix, const uint64_t* __restrict__ rows,
-                                               uint64_t total, uint64_t chunk,
-                                               uint64_t* __restrict__ out,
-                                               unsigned long long* __restrict__ err,
-                                               uint32_t steps_only) {
-  enum : uint32_t { kFetch = 0, kWalk = 1, kSample = 2, kDone = 3 };
-  __shared__ NodeTable T;
-  __shared__ unsigned long long next;
-  const uint64_t a = blockIdx.x * chunk;
-  const uint64_t end = (a + chunk < total) ? a + chunk : total;
-  load_table(T, ix.table);
-  if (threadIdx.x == 0) next = a;
-  __syncthreads();
-  if (a >= total) return;
-  const uint64_t n = ix.n;
-  uint64_t j = 0, pos = 0, steps = 0, adj = 0;
-  uint32_t phase = kFetch;
-  for (;;) {
-    if (phase == kFetch) {
-      j = atomicAdd(&next, 1ull);
-      if (j >= end) phase = kDone;
-    }
-    if (!__any(phase != kDone)) break;
-    uint64_t row = 0, smp = 0;
-    if (phase == kFetch) row = rows[j];
-    if (phase == kSample) smp = ssa_at(ix, sample_index<POW2>(ix, pos));
-    if (phase == kFetch) {
-      pos = row & kWalkRowMask;
-      adj = row >> kWalkAdjShift;
-      steps = 0;
-      phase = kWalk;
-    } else if (phase == kSample) {
-      uint64_t s = smp + steps;  // :147-153
-      s = s >= n ? s - n : s;
-      st_out(out + j, steps_only ? steps : s >= adj ? s - adj : s + n - adj);
-      phase = kFetch;
-    } else if (phase == kWalk) {
-      // loop condition of fm_index.cpp:130: stop at a sampled row or after n steps
-      if (is_sampled<POW2>(ix, pos) || steps >= n) {
-        if (steps >= n) {
-          atomicMin(err, (unsigned long long)j);  // fm_index.cpp:136-138
-          phase = kFetch;
-        } else {
-          phase = kSample;
-        }
-      } else {
-        pos = E::lf(ix, T, pos);
-        ++steps;
-      }
-    }
-  }
-}
-
-// The same walk over walk lines (occurrence engine, fm_device.hpp WalkLine): one
-// line per step gives the mark, the sample index and LF.
-__device__ __forceinline__ uint64_t wssa_at(const DevIndex& ix, uint64_t k) {
-  if (ix.wssa_eb == 5) {  // 40-bit entries (wide position samples): the two dwords holding them
-    const uint64_t b = 5 * k;
-    const uint32_t* d = static_cast<const uint32_t*>(ix.wssa) + (b >> 2);
-    const uint64_t x = ((uint64_t)d[1] << 32) | d[0];
-    return (x >> (8 * (b & 3))) & ((1ull << 40) - 1);
-  }
-  return ix.wssa_eb == 8 ? static_cast<const uint64_t*>(ix.wssa)[k] : static_cast<const uint32_t*>(ix.wssa)[k];
-}
-
-// LF(pos) from pos's walk line v (line q, offset o): C[c] + occ(c, pos) from the same
-// line (OccE::lf), or for the quaternary matrix level 0 from the walk line and levels
-// 1.. as QWM::lf.
-template <class W, bool kQ>
-__device__ __forceinline__ uint64_t walk_lf(const DevIndex& ix, const NodeTable& T,
-                                            const typename W::Raw& v, uint64_t q, uint32_t o,
-                                            uint64_t pos) {
-  if (!kQ) {
-    const uint32_t code = W::code(v, o);
-    uint32_t c = T.occ_sym[code];
-    uint64_t r = W::occ(v, code, q, o);
-    if (code == 0 && T.exc_n) {
-      const uint32_t e = exc_before(T, pos);
-      if (e < T.exc_n && T.exc_row[e] == pos) {
-        c = T.exc_sym[e];
-        r = exc_rank(T, c, pos);
-      } else {
-        r -= e;
-      }
-    }
-    return T.C[c] + r;
-  }
-  const uint32_t d0 = W::code(v, o);
-  uint64_t p = T.qZ[0][d0] + W::occ(v, d0, q, o);
-  uint32_t x = d0;
-  const int L = (int)T.qlevels;
-  for (int l = 1; l < L; ++l) {
-    const int nid = qnode_id(l, x);
-    const uint8_t f = T.flags[nid];
-    uint32_t d;
-    if (f & kPure) {
-      d = (f >> 2) & 3u;
-      p = T.qZ[l][d] + T.R[nid] + (p - T.S[nid]);
-    } else {
-      OccLine::Raw lv;
-      const uint64_t lq = p >> 6;
-      OccLine::load(QWM::level(ix, l), lq, lv);
-      const uint32_t lo = (uint32_t)(p & 63);
-      d = OccLine::code(lv, lo);
-      p = T.qZ[l][d] + OccLine::base(lv, d, lq) + OccLine::prefix(lv, d, lo);
-    }
-    x = (x << 2) | d;
-  }
-  return T.C[T.qsym[x]] + (p - T.S8[x]);
-}
-
-// Short walks (walk lines with text-position marks, lf_exact): every walk ends within
-// pstride - 1 steps, so one lane per reported row — coalesced row reads, no work
-// queue — and finished waves make room for new ones, as in the count kernels.
-// One short walk (walk lines with text-position marks): from BWT row `pos` by LF to the
-// first marked row or row the reference samples; writes out[j] = its text position
-// minus adj (mod n), or the LF steps when steps_only; an overrun records j in err.
-template <class W, bool kQ>
-__device__ __forceinline__ void walk_short_one(const DevIndex& ix, const NodeTable& T, uint64_t pos,
-                                               uint64_t adj, uint64_t j, uint64_t* __restrict__ out,
-                                               unsigned long long* __restrict__ err,
-                                               uint32_t steps_only) {
-  const uint64_t n = ix.n;
-  const uint64_t row_mask = ix.stride_shift != 0xFFFFFFFFu ? (1ull << ix.stride_shift) - 1 : 0;
-  uint64_t steps = 0;
-  for (;;) {
-    uint64_t q;
-    uint32_t o;
-    typename W::Raw v;
-    W::locate(pos, q, o);
-    W::load(ix.walk, q, v);
-    const bool mk = W::mark(v, o);
-    const bool rs = row_mask ? (pos & row_mask) == 0 : pos % ix.stride == 0;
-    if (mk || rs || steps >= n) {  // fm_index.cpp:130 loop condition
-      if (steps >= n) {            // :136-138
-        atomicMin(err, (unsigned long long)j);
-        return;
-      }
-      const uint64_t sidx = mk ? W::mark_rank(v, o) : (row_mask ? pos >> ix.stride_shift : pos / ix.stride);
-      uint64_t s = (mk ? wssa_at(ix, sidx) : ssa_at(ix, sidx)) + steps;  // :147-153
-      s = s >= n ? s - n : s;
-      st_out(out + j, steps_only ? steps : s >= adj ? s - adj : s + n - adj);
-      return;
-    }
-    pos = walk_lf<W, kQ>(ix, T, v, q, o, pos);
-    ++steps;
-  }
-}
-
-template <class W>
-__device__ __forceinline__ uint64_t walk_position(const DevIndex& ix, const NodeTable& T, uint64_t pos) {
-  // as walk_short_one; an lf_exact index with text-position marks ends every walk within
-  // pstride - 1 steps (the bound below is never reached)
-  const uint64_t n = ix.n;
-  const uint64_t row_mask = ix.stride_shift != 0xFFFFFFFFu ? (1ull << ix.stride_shift) - 1 : 0;
-  for (uint64_t steps = 0; steps < n; ++steps) {
-    uint64_t q;
-    uint32_t o;
-    typename W::Raw v;
-    W::locate(pos, q, o);
-    W::load(ix.walk, q, v);
-    const bool mk = W::mark(v, o);
-    const bool rs = row_mask ? (pos & row_mask) == 0 : pos % ix.stride == 0;
-    if (mk || rs) {  // fm_index.cpp:147-153
-      const uint64_t sidx = mk ? W::mark_rank(v, o) : (row_mask ? pos >> ix.stride_shift : pos / ix.stride);
-      const uint64_t s = (mk ? wssa_at(ix, sidx) : ssa_at(ix, sidx)) + steps;
-      return s >= n ? s - n : s;
-    }
-    pos = walk_lf<W, false>(ix, T, v, q, o, pos);
-  }
-  return 0;
-}
-
-// walk_position and the LF steps it took (measurement twin: bench.py's walk bytes)
-template <class W>
-__device__ __forceinline__ uint64_t walk_position_steps(const DevIndex& ix, const NodeTable& T, uint64_t pos,
-                                                        uint64_t& steps_out) {
-  const uint64_t n = ix.n;
-  const uint64_t row_mask = ix.stride_shift != 0xFFFFFFFFu ? (1ull << ix.stride_shift) - 1 : 0;
-  for (uint64_t steps = 0; steps < n; ++steps) {
-    uint64_t q;
-    uint32_t o;
-    typename W::Raw v;
-    W::locate(pos, q, o);
-    W::load(ix.walk, q, v);
-    const bool mk = W::mark(v, o);
-    const bool rs = row_mask ? (pos & row_mask) == 0 : pos % ix.stride == 0;
-    if (mk || rs) {
-      const uint64_t sidx = mk ? W::mark_rank(v, o) : (row_mask ? pos >> ix.stride_shift : pos / ix.stride);
-      const uint64_t s = (mk ? wssa_at(ix, sidx) : ssa_at(ix, sidx)) + steps;
-      steps_out = steps;
-      return s >= n ? s - n : s;
-    }
-    pos = walk_lf<W, false>(ix, T, v, q, o, pos);
-  }
-  steps_out = n;
-  return 0;
-}
-
-template <class W, int U>
-__device__ __forceinline__ void walk_positions(const DevIndex& ix, const NodeTable& T, uint64_t* pos,
-                                               bool* act) {
-  const uint64_t n = ix.n;
-  const uint64_t row_mask = ix.stride_shift != 0xFFFFFFFFu ? (1ull << ix.stride_shift) - 1 : 0;
-  uint64_t steps[U];
-#pragma unroll
-  for (int j = 0; j < U; ++j) steps[j] = 0;
-  for (uint64_t it = 0; it < n; ++it) {
-    bool any = false;
-#pragma unroll
-    for (int j = 0; j < U; ++j) any |= act[j];
-    if (!any) return;
-    uint64_t q[U];
-    uint32_t o[U];
-    typename W::Raw v[U];
-#pragma unroll
-    for (int j = 0; j < U; ++j) {  // the lines of every active walk first
-      q[j] = 0, o[j] = 0;
-      if (act[j]) {
-        W::locate(pos[j], q[j], o[j]);
-        W::load(ix.walk, q[j], v[j]);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      if (!act[j]) continue;
-      const bool mk = W::mark(v[j], o[j]);
-      const bool rs = row_mask ? (pos[j] & row_mask) == 0 : pos[j] % ix.stride == 0;
-      if (mk || rs) {  // fm_index.cpp:147-153
-        const uint64_t sidx = mk ? W::mark_rank(v[j], o[j])
-                                 : (row_mask ? pos[j] >> ix.stride_shift : pos[j] / ix.stride);
-        const uint64_t s = (mk ? wssa_at(ix, sidx) : ssa_at(ix, sidx)) + steps[j];
-        pos[j] = s >= n ? s - n : s;
-        act[j] = false;
-      } else {
-        pos[j] = walk_lf<W, false>(ix, T, v[j], q[j], o[j], pos[j]);
-        ++steps[j];
-      }
-    }
-  }
-}
-
-// walk_lf over the occurrence-line walk lines with the step's constants in registers (K);
-// more than one rare row takes the table (through the caches) as walk_lf does
-template <class W>
-__device__ __forceinline__ uint64_t walk_lf_k(const NodeTable& T, const WalkK& K, const typename W::Raw& v,
-                                              uint64_t q, uint32_t o, uint64_t pos) {
-  const uint32_t code = W::code(v, o);
-  uint64_t r = W::occ(v, code, q, o);
-  const uint64_t cc = code == 0 ? K.C[0] : code == 1 ? K.C[1] : code == 2 ? K.C[2] : K.C[3];
-  if (code == 0 && K.nexc) {
-    if (K.nexc == 1) {
-      if (pos == K.exc_row0) return K.exc_c0;  // the rare row: no earlier row holds its symbol
-      r -= K.exc_row0 < pos ? 1u : 0u;
-    } else {
-      const uint32_t e = exc_before(T, pos);
-      if (e < T.exc_n && T.exc_row[e] == pos) {
-        const uint32_t c = T.exc_sym[e];
-        return T.C[c] + exc_rank(T, c, pos);
-      }
-      r -= e;
-    }
-  }
-  return cc + r;
-}
-
-template <class W, int U>
-__device__ __forceinline__ void walk_positions_k(const DevIndex& ix, const NodeTable& T, const WalkK& K,
-                                                 uint64_t* pos, bool* act) {
-  const uint64_t n = ix.n;
-  const uint64_t row_mask = ix.stride_shift != 0xFFFFFFFFu ? (1ull << ix.stride_shift) - 1 : 0;
-  uint64_t steps[U];
-#pragma unroll
-  for (int j = 0; j < U; ++j) steps[j] = 0;
-  for (uint64_t it = 0; it < n; ++it) {
-    bool any = false;
-#pragma unroll
-    for (int j = 0; j < U; ++j) any |= act[j];
-    if (!any) return;
-    uint64_t q[U];
-    uint32_t o[U];
-    typename W::Raw v[U];
-#pragma unroll
-    for (int j = 0; j < U; ++j) {  // the lines of every active walk first
-      q[j] = 0, o[j] = 0;
-      if (act[j]) {
-        W::locate(pos[j], q[j], o[j]);
-        W::load(ix.walk, q[j], v[j]);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      if (!act[j]) continue;
-      const bool mk = W::mark(v[j], o[j]);
-      const bool rs = row_mask ? (pos[j] & row_mask) == 0 : pos[j] % ix.stride == 0;
-      if (mk || rs) {  // fm_index.cpp:147-153
-        const uint64_t sidx = mk ? W::mark_rank(v[j], o[j])
-                                 : (row_mask ? pos[j] >> ix.stride_shift : pos[j] / ix.stride);
-        const uint64_t s = (mk ? wssa_at(ix, sidx) : ssa_at(ix, sidx)) + steps[j];
-        pos[j] = s >= n ? s - n : s;
-        act[j] = false;
-      } else {
-        pos[j] = walk_lf_k<W>(T, K, v[j], q[j], o[j], pos[j]);
-        ++steps[j];
-      }
-    }
-  }
-}
-
-template <class W, bool kQ>
-__global__ __launch_bounds__(kBlk) void k_walk_short(DevIndex ix, const uint64_t* __restrict__ rows,
-                                                     uint64_t total, uint64_t* __restrict__ out,
-                                                     unsigned long long* __restrict__ err,
-                                                     uint32_t steps_only) {
-  __shared__ NodeTable T;
-  load_table(T, ix.table);
-  __syncthreads();
-  const uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-  if (j >= total) return;
-  const uint64_t row = rows[j];
-  walk_short_one<W, kQ>(ix, T, row & kWalkRowMask, row >> kWalkAdjShift, j, out, err, steps_only);
-}
-
-// Phase 2 over walk lines with text-position marks, fused with the records (no rows
-// buffer, as k_locate_sa for the full SA): a lane takes a pattern's reported rows —
-// a context window's matching rows (subtracting k) or a plain range of at most
-// kLocSmall rows — and walks each; wider ranges are listed for k_walk_fused_wide.
-template <class W, bool kQ>
-__global__ __launch_bounds__(kBlk) void k_walk_fused(DevIndex ix, const uint64_t* __restrict__ sp,
-                                                     const uint64_t* __restrict__ offs, uint64_t npat,
-                                                     uint64_t* __restrict__ out,
-                                                     uint64_t* __restrict__ wide,
-                                                     unsigned long long* __restrict__ nwide,
-                                                     unsigned long long* __restrict__ err,
-                                                     uint32_t steps_only) {
-  __shared__ NodeTable T;
-  load_table(T, ix.table);
-  __syncthreads();
-  const uint64_t q = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-  if (q >= npat) return;
-  const uint64_t a = offs[q], c = offs[q + 1] - a, s = sp[q];
-  if (!c) return;
-  if (s & kLocCtx) {
-    const uint64_t r0 = s & kLocRowMask, adj = (s >> 60) & 7u;
-    uint32_t rel = (uint32_t)(s >> 38) & ((1u << kLocSpanBits) - 1u);
-    for (uint64_t j = 0; j < c; ++j) {
-      const uint32_t f = (uint32_t)__ffs(rel) - 1u;
-      walk_short_one<W, kQ>(ix, T, r0 + f, adj, a + j, out, err, steps_only);
-      rel &= rel - 1u;
-    }
-  } else if (c <= kLocSmall) {
-    for (uint64_t j = 0; j < c; ++j) walk_short_one<W, kQ>(ix, T, s + j, 0, a + j, out, err, steps_only);
-  } else {
-    wide[atomicAdd(nwide, 1ull)] = q;
-  }
-}
-
-// the listed wide ranges: a block per range, its threads over the rows
-template <class W, bool kQ>
-__global__ __launch_bounds__(kBlk) void k_walk_fused_wide(DevIndex ix, const uint64_t* __restrict__ sp,
-                                                          const uint64_t* __restrict__ offs,
-                                                          uint64_t* __restrict__ out,
-                                                          const uint64_t* __restrict__ wide,
-                                                          const unsigned long long* __restrict__ nwide,
-                                                          unsigned long long* __restrict__ err,
-                                                          uint32_t steps_only) {
-  __shared__ NodeTable T;
-  load_table(T, ix.table);
-  __syncthreads();
-  const uint64_t nw = *nwide;
-  for (uint64_t e = blockIdx.x; e < nw; e += gridDim.x) {
-    const uint64_t q = wide[e], a = offs[q], c = offs[q + 1] - a, s = sp[q];
-    for (uint64_t j = threadIdx.x; j < c; j += blockDim.x)
-      walk_short_one<W, kQ>(ix, T, s + j, 0, a + j, out, err, steps_only);
-  }
-}
-
-template <class W, bool kQ>
-__global__ __launch_bounds__(kBlk) void k_walk_lines(DevIndex ix, const uint64_t* __restrict__ rows,
-                                                     uint64_t total, uint64_t chunk,
-                                                     uint64_t* __restrict__ out,
-                                                     unsigned long long* __restrict__ err,
-                                                     uint32_t steps_only) {
-  // Each lane cycles FETCH (row from the block's slice) -> WALK (one line per LF
-  // step) -> SAMPLE (the mark's SA sample, with the next row's index) -> WALK ...
-  // Every loop iteration issues at most one dependent load per lane and kind,
-  // whatever its phase, so a wave waits one memory round trip per iteration even
-  // when some of its lanes are starting or finishing a walk.
-  enum : uint32_t { kFetch = 0, kWalk = 1, kSample = 2, kDone = 3 };
-  __shared__ NodeTable T;
-  __shared__ unsigned long long next;
-  const uint64_t a = blockIdx.x * chunk;
-  const uint64_t end = (a + chunk < total) ? a + chunk : total;
-  load_table(T, ix.table);
-  if (threadIdx.x == 0) next = a;
-  __syncthreads();
-  if (a >= total) return;
-  const uint64_t n = ix.n;
-  uint64_t j = 0, pos = 0, steps = 0, sidx = 0, adj = 0;
-  uint32_t phase = kFetch;
-  bool from_ssa = false;  // the stop row is one of the reference's sampled rows
-  const uint64_t row_mask = ix.stride_shift != 0xFFFFFFFFu ? (1ull << ix.stride_shift) - 1 : 0;
-  for (;;) {
-    if (phase == kFetch) {
-      j = atomicAdd(&next, 1ull);
-      if (j >= end) phase = kDone;
-    }
-    if (!__any(phase != kDone)) break;
-    // ---- issue this iteration's load ----
-    uint64_t row = 0, smp = 0, q = 0;
-    uint32_t o = 0;
-    typename W::Raw v;
-    if (phase == kFetch) row = rows[j];
-    if (phase == kWalk) {
-      W::locate(pos, q, o);
-      W::load(ix.walk, q, v);
-    }
-    uint64_t jn = 0;
-    if (phase == kSample) {
-      smp = from_ssa ? ssa_at(ix, sidx) : wssa_at(ix, sidx);
-      // the next row's index travels with the sample: a walk of s steps costs s + 1
-      // round trips instead of s + 2 (walks average ~3 steps at pstride 8)
-      jn = atomicAdd(&next, 1ull);
-      if (jn < end) row = rows[jn];
-    }
-    // ---- consume ----
-    if (phase == kFetch) {
-      pos = row & kWalkRowMask;
-      adj = row >> kWalkAdjShift;
-      steps = 0;
-      phase = kWalk;
-    } else if (phase == kWalk) {
-      // a walk may stop at a marked row or at a row the reference samples
-      // (row % stride == 0, SSA): both give SA[start] = sample + steps, and the
-      // first of the two comes sooner (mean 11 steps at stride 32 instead of 15.5)
-      const bool mk = W::mark(v, o);
-      const bool rs = row_mask ? (pos & row_mask) == 0 : pos % ix.stride == 0;
-      if (mk || rs || steps >= n) {  // fm_index.cpp:130 loop condition
-        if (steps >= n) {            // :136-138, checked first
-          atomicMin(err, (unsigned long long)j);
-          phase = kFetch;
-        } else {
-          from_ssa = !mk;
-          sidx = mk ? W::mark_rank(v, o) : (row_mask ? pos >> ix.stride_shift : pos / ix.stride);
-          phase = kSample;
-        }
-      } else {
-        pos = walk_lf<W, kQ>(ix, T, v, q, o, pos);
-        ++steps;
-      }
-    } else if (phase == kSample) {
-      uint64_t s = smp + steps;  // :147-153
-      s = s >= n ? s - n : s;
-      st_out(out + j, steps_only ? steps : s >= adj ? s - adj : s + n - adj);
-      if (jn < end) {
-        j = jn;
-        pos = row & kWalkRowMask;
-        adj = row >> kWalkAdjShift;
-        steps = 0;
-        phase = kWalk;
-      } else {
-        phase = kDone;
-      }
-    }
-  }
-}
-
 // ---- building-block kernels for parity tests ----
 template <class F>
 __global__ void k_level_rank1(DevIndex ix, int level, const uint64_t* __restrict__ pos, uint64_t k,
@@ -4309,95 +3688,6 @@ cs_status launch_locate_ranges(const cs_fm_index* h, const uint8_t* d_pats,
   return CS_OK;
 }
 
-cs_status launch_locate_walk(const cs_fm_index* h, const uint64_t* d_sp,
-                             const uint64_t* d_out_offs, uint64_t npat, uint64_t total,
-                             uint64_t* d_out_pos, hipStream_t st, unsigned long long* err_word,
-                             uint32_t flags, uint32_t steps_only) {
-  if (!total) return CS_OK;
-  flags = call_flags(h, flags);
-  if (h->d_sa && h->lf_exact && !(flags & CS_Q_NO_FULL_SA)) {  // full suffix array: one read per position
-    if (steps_only) {  // no LF steps: one SA read per position
-      FMX_HIP(hipMemsetAsync(d_out_pos, 0, total * 8, st));
-      return CS_OK;
-    }
-    StreamBuf wide;
-    FMX_HIP(wide.alloc((total / (kLocSmall + 1) + 1) * 8 + 8, st));
-    unsigned long long* nwide = wide.as<unsigned long long>();
-    FMX_HIP(hipMemsetAsync(nwide, 0, 8, st));
-    const uint32_t* sa = static_cast<const uint32_t*>(h->d_sa);
-    k_locate_sa<<<grid_for(npat, kBlk, 0xFFFFFFFFu), kBlk, 0, st>>>(
-        sa, h->n, d_sp, d_out_offs, npat, d_out_pos, wide.as<uint64_t>() + 1, nwide);
-    FMX_HIP(hipGetLastError());
-    k_locate_sa_wide<<<1024, kBlk, 0, st>>>(sa, d_sp, d_out_offs, d_out_pos,
-                                             wide.as<uint64_t>() + 1, nwide);
-    FMX_HIP(hipGetLastError());
-    return CS_OK;
-  }
-  int dev = 0, ncu = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  const uint64_t max_blocks = (uint64_t)ncu * 8;  // 8 x 256 threads = full CU
-  uint64_t chunk = (total + max_blocks - 1) / max_blocks;
-  if (chunk < 64) chunk = 64;
-  const unsigned blocks = (unsigned)((total + chunk - 1) / chunk);
-  const DevIndex ix = query_dev(h, flags);
-  unsigned long long* err =
-      err_word ? err_word : reinterpret_cast<unsigned long long*>(h->d_err);
-  // short_walk: walk lines with text-position marks, a short walk per position; unless
-  // CS_QT_WALK_PERSISTENT (CS_FM_WALK_PERSISTENT=1): the persistent walk over a rows buffer
-  const bool short_walk = ix.walk && h->walk_marks == 2 && !(flags & CS_QT_WALK_PERSISTENT);
-  // fused: the short walks straight from the records (no rows buffer); unless CS_QT_WALK_ROWS
-  // (CS_FM_WALK_ROWS=1): from an expanded rows buffer (k_expand_rows + k_walk_short)
-  const bool fused = short_walk && !(flags & CS_QT_WALK_ROWS);
-  // qwm: the walk lines are a quaternary matrix's (kQ); pow2: the sample stride is a power
-  // of two (POW2; the persistent walk over the engine, an index without walk lines)
-  const bool qwm = h->line_fmt == kFmtQwm;
-  const bool pow2 = ix.stride_shift != 0xFFFFFFFFu;
-  if (fused) {
-    StreamBuf wide;
-    FMX_HIP(wide.alloc((total / (kLocSmall + 1) + 1) * 8 + 8, st));
-    unsigned long long* nwide = wide.as<unsigned long long>();
-    FMX_HIP(hipMemsetAsync(nwide, 0, 8, st));
-    uint64_t* wl = wide.as<uint64_t>() + 1;
-    const unsigned g = grid_for(npat, kBlk, 0xFFFFFFFFu);
-    with_walk_line(h->wide, [&](auto line) {
-      with_bool(qwm, [&](auto kQ) {
-        using W = typename decltype(line)::type;
-        k_walk_fused<W, kQ><<<g, kBlk, 0, st>>>(ix, d_sp, d_out_offs, npat, d_out_pos, wl, nwide, err, steps_only);
-        k_walk_fused_wide<W, kQ><<<1024, kBlk, 0, st>>>(ix, d_sp, d_out_offs, d_out_pos, wl, nwide, err, steps_only);
-      });
-    });
-    FMX_HIP(hipGetLastError());
-    return CS_OK;
-  }
-  StreamBuf rows;
-  FMX_HIP(rows.alloc(total * 8, st));
-  k_expand_rows<<<grid_for(npat, kBlk, 65536), kBlk, 0, st>>>(d_sp, d_out_offs, npat,
-                                                              rows.as<uint64_t>());
-  FMX_HIP(hipGetLastError());
-  const uint64_t* r = rows.as<uint64_t>();
-  if (ix.walk) {  // over walk lines: the short walks, or the persistent walk
-    with_walk_line(h->wide, [&](auto line) {
-      with_bool(qwm, [&](auto kQ) {
-        using W = typename decltype(line)::type;
-        if (short_walk)
-          k_walk_short<W, kQ><<<grid_for(total, kBlk, 0xFFFFFFFFu), kBlk, 0, st>>>(ix, r, total, d_out_pos, err, steps_only);
-        else
-          k_walk_lines<W, kQ><<<blocks, kBlk, 0, st>>>(ix, r, total, chunk, d_out_pos, err, steps_only);
-      });
-    });
-  } else {  // the persistent walk over the engine's own LF
-    with_engine(h->line_fmt, [&](auto engine) {
-      with_bool(pow2, [&](auto POW2) {
-        using E = typename decltype(engine)::type;
-        k_walk<E, POW2><<<blocks, kBlk, 0, st>>>(ix, r, total, chunk, d_out_pos, err, steps_only);
-      });
-    });
-  }
-  FMX_HIP(hipGetLastError());
-  return CS_OK;  // rows are freed in stream order after the walk
-}
-
 void keep_pool(int device) {
   static std::once_flag once[64];
   if (device < 0 || device >= 64) return;
@@ -4411,18 +3701,6 @@ void keep_pool(int device) {
     (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
     (void)hipGetLastError();
   });
-}
-
-cs_status check_locate_error(const cs_fm_index* h, unsigned long long* err, hipStream_t st) {
-  if (!err) err = reinterpret_cast<unsigned long long*>(h->d_err);
-  uint64_t bad = ~0ull;
-  FMX_HIP(hipMemcpyAsync(&bad, err, 8, hipMemcpyDeviceToHost, st));
-  FMX_HIP(hipStreamSynchronize(st));
-  if (bad == ~0ull) return CS_OK;
-  FMX_HIP(hipMemsetAsync(err, 0xFF, 8, st));
-  FMX_HIP(hipStreamSynchronize(st));
-  set_error("locate: LF walk exceeded text length");  // fm_index.cpp:137
-  return CS_ERR_LF_OVERRUN;
 }
 
 cs_status launch_level_rank1(const cs_fm_index* h, int level, const uint64_t* d_pos, uint64_t k,

@@ -1,5 +1,5 @@
 // fm_search.hpp — device-side search helpers shared by the query kernels (fm_query.hip,
-// fm_mismatch.hip) and the index-structure builders (fm_structs.hip): the node table in LDS, one
+// fm_walk.hip, fm_mismatch.hip) and the index-structure builders (fm_structs.hip): the node table in LDS, one
 // backward-search step per rank engine, the prefix-table / left-context / record
 // lookups and the search loops the kernels are built from, plus the dispatch helpers
 // (with_engine, with_walk_line, with_bool, with_int).  Everything sits in an anonymous
@@ -700,6 +700,14 @@ __device__ __forceinline__ uint64_t count_pattern(const DevIndex& ix, const Node
 __device__ __forceinline__ uint32_t load_sa(const uint32_t* sa, uint64_t r) {
   return __builtin_nontemporal_load(sa + r);
 }
+// Locate's outputs (offsets and positions) leave through non-temporal stores: nothing on the
+// device reads them again (C4 one call 0.853 -> 0.818 ms in an A/B on one box; the search
+// kernel's records and counts, which the emit kernel reads back, measured the same either
+// way: profiles/r03/ab_nt_locate.jsonl)
+template <class T>
+__device__ __forceinline__ void st_out(T* p, T v) {
+  __builtin_nontemporal_store(v, p);
+}
 
 // Verification against the text (lf_exact indexes that keep the full suffix array and the
 // text in HBM: DevIndex::vsa / vtext).  Row r of [sp, ep) survives the k remaining steps
@@ -1183,6 +1191,44 @@ __device__ __forceinline__ void loc_window(uint64_t s, uint64_t& r0, uint64_t& a
     adj = (s >> 50) & kLocVerMaxK;
   }
 }
+// The same for a record phase 2 walks (k_walk_fused, k_expand_rows: fm_walk.hip): a context
+// window only.  No verified window reaches a walk: locate_search writes one only where
+// DevIndex::vsa is set — an index that keeps the full suffix array, and not under
+// CS_Q_NO_FULL_SA (query_dev) — while launch_locate_walk walks only an index without the
+// full suffix array or under that flag, and the two phases of a locate run under the same
+// flags; the mismatch locates hand it plain ranges.  (A verified window's k, up to
+// kLocVerMaxK, would not fit the 8 bits over kWalkAdjShift of a walk row.)
+__device__ __forceinline__ void loc_ctx_window(uint64_t s, uint64_t& r0, uint64_t& adj, uint32_t& rel) {
+  r0 = s & kLocRowMask;
+  adj = (s >> 60) & 7u;
+  rel = (uint32_t)(s >> 38) & ((1u << kLocSpanBits) - 1u);
+}
+
+// The reported rows of a locate record in row order (fm_index.cpp:125), one per next(): the
+// rows s, s + 1, ... of a plain range, or a window's matching rows, each `adj` characters
+// before its position.  The caller takes as many as the pattern reports (min(count, limit)).
+struct LocRows {
+  uint64_t r0;       // the next row of a plain range; a window's first row
+  uint64_t adj = 0;  // positions to subtract (a window's k)
+  uint32_t rel = 0;  // a window's matches not yet taken (bit i: row r0 + i)
+  __device__ __forceinline__ explicit LocRows(uint64_t s) : r0(s) {}
+  static __device__ __forceinline__ LocRows of(uint64_t s) {  // any record
+    LocRows it(s);
+    if (s & kLocCtx) loc_window(s, it.r0, it.adj, it.rel);
+    return it;
+  }
+  static __device__ __forceinline__ LocRows of_walk(uint64_t s) {  // a record phase 2 walks
+    LocRows it(s);
+    if (s & kLocCtx) loc_ctx_window(s, it.r0, it.adj, it.rel);
+    return it;
+  }
+  __device__ __forceinline__ uint64_t next() {
+    if (!rel) return r0++;
+    const uint64_t row = r0 + (uint32_t)__ffs(rel) - 1u;
+    rel &= rel - 1u;
+    return row;
+  }
+};
 
 // The rows base + i (bit i of mm) whose window text[SA - k, SA - qf) spells P[0, k - qf)
 // (verify_rows' test, as a mask).
