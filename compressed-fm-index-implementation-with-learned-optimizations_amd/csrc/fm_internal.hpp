@@ -237,7 +237,8 @@ struct Work {
   void* p = nullptr;
   uint64_t bytes = 0;
 };
-// workspace bytes of a routed count / a one-call locate of npat patterns (fm_query.hip)
+// workspace bytes of a routed count (fm_query.hip) / a one-call locate (fm_locate.hip) of
+// npat patterns
 uint64_t count_workspace_bytes(const cs_fm_index* h, uint64_t npat);
 uint64_t locate_workspace_bytes(const cs_fm_index* h, uint64_t npat);
 // the tuning defaults of a new handle from the CS_FM_* environment (cs_fm_index::tune,
@@ -267,8 +268,8 @@ class BuildOptScope {
 // offending token in err for a malformed pair or a name no builder reads
 bool parse_build_options(const char* text, BuildOptions& o, std::string& err);
 
-// Query launches (fm_query.hip; locate's phase 2 in fm_walk.hip, the mismatch family's in
-// fm_mismatch.hip).
+// Query launches (fm_query.hip; locate's phase 2 in fm_walk.hip, the one-call locate's finish
+// in fm_locate.hip, the mismatch family's in fm_mismatch.hip).
 // the call's flags with the handle's tuning defaults
 inline uint32_t call_flags(const cs_fm_index* h, uint32_t flags) { return flags | h->tune; }
 // the index as one query sees it under the caller's query flags (fm_query.hip)

@@ -19,9 +19,11 @@
 //
 // locate: (1) the same search writes sp and min(count, limit); (2) exclusive scan ->
 // CSR offsets; then phase 2, the positions of the reported rows (fm_walk.hip).  The
-// one-call locate (below) does the three in one call; its walks, and those of
-// k_count_long's walk-verify forms, are fm_walk.hpp's.
-#include "fm_walk.hpp"
+// one-call locate does the three in one call: its searches are here, the contract through
+// which they hand their results over is fm_locate.hpp's (OnePass, locate_split_store,
+// wave_tile_add) and its finish — tile scan, emit, listed walks, wide ranges — fm_locate.hip's;
+// its walks, and those of k_count_long's walk-verify forms, are fm_walk.hpp's.
+#include "fm_locate.hpp"
 
 namespace fmx {
 namespace {
@@ -160,530 +162,6 @@ __device__ __forceinline__ void general_rest(const DevIndex& ix, const NodeTable
   }
 }
 
-// Batch locate in one call (cs_fm_locate_device) over an index that keeps the full suffix
-// array: three launches and one host synchronisation —
-//   (1) k_count_ctx with kOne: the staged search; per pattern its record and, unless the
-//       record is the pattern's only position (kLocStash below: count 1, 99.6 % of C4
-//       Q_text), min(count, limit) — 8 B written per pattern instead of 12;
-//       Per tile (a search block's 2 x 256 patterns) the total, added by each wave.
-//   (2) k_scan_tiles: the exclusive scan of the tile totals (one block; C4: 24 k tiles);
-//   (3) k_locate_emit: per tile, the block's scan of its counts plus the tile's prefix
-//       give the output offsets, then the positions straight from the records through SA.
-// (A look-back inside the search kernel, measured in round 3, made every block wait for the
-// slowest search among its predecessors: 3.2 ms against 1.1 ms; the other forms round 5
-// tried are listed at k_locate_emit.)  Against the two phases this drops the scan of a
-// 100-MB count array and the host round trip between the phases.
-// Indexes without the full suffix array but with walk lines and text-position marks (C5;
-// C4 under CS_FM_FULL_SA=0) take the same launches (round 3): a position is the
-// short walk from its row (walk_position: at most pstride - 1 LF steps, one 32-B walk line
-// each, then the mark's sample) instead of SA[row], in (1) for a pattern's only position
-// and in (3) / k_locate_emit_wide for the rest (kPos: 0 the full SA, 1 WalkLine, 2
-// WalkLineW).  Counts are u64 (cnt64) when the index is wide.
-// The outputs (offsets and positions) leave through non-temporal stores (st_out).
-struct OnePass {
-  uint32_t* cnt = nullptr;               // (1) -> (3): min(count, limit) per pattern (narrow),
-                                         // unless its record is a stashed position (count 1)
-  uint64_t* cnt64 = nullptr;             // the same, wide indexes
-  uint64_t* rec = nullptr;               // (1) -> (3): the pattern's record
-  uint64_t* tiles = nullptr;             // per tile (a search block's patterns): its total, then
-                                         // its exclusive prefix (k_scan_tiles)
-  const uint32_t* sa = nullptr;          // full suffix array
-  uint64_t* out_offs = nullptr;          // npat + 1 exclusive offsets
-  uint64_t* out_pos = nullptr;           // positions, `cap` of them
-  uint64_t cap = 0;
-  uint64_t* wide = nullptr;              // (q, first row) of ranges over kLocSmall rows
-  unsigned long long* nwide = nullptr;
-  uint64_t wide_cap = 0;
-  uint32_t defer = 0;  // locate records: a pattern its record does not answer -> k_locate_list
-  // walk-line indexes (kPos 1 / 2): the positions of patterns with 2..kLocSmall rows, as
-  // (output index, row | adj << kWalkAdjShift) pairs for k_locate_walks — one lane per position, so no
-  // emit wave waits on a lane's chain of walks — kLocTile slots per tile (tile t's at
-  // t kLocTile, their number in wcnt[t]: no global counter); past them the emit walks them
-  uint64_t* walks = nullptr;
-  uint32_t* wcnt = nullptr;
-  // k_scan_chained: per scan block its published total (bit 63: ready), zeroed by the search
-  // kernel's block 0 (or a memset where no search kernel runs)
-  unsigned long long* sflags = nullptr;
-};
-constexpr uint32_t kScanBlock = 1024;     // tiles per block of k_scan_chained
-constexpr uint32_t kScanMaxBlocks = 1024; // (its look-back: one predecessor per thread)
-__device__ __forceinline__ void onepass_zero(const OnePass& op) {
-  // the call's wide-range counter and the chained scan's flags and ticket (no memset launch;
-  // stream order makes the stores visible to the kernels after this one)
-  if (threadIdx.x == 0) {
-    if (blockIdx.x == 0) *op.nwide = 0;
-    if (op.sflags && blockIdx.x < kScanMaxBlocks) op.sflags[blockIdx.x] = 0;
-    if (op.sflags && blockIdx.x == 0) op.sflags[kScanMaxBlocks] = 0;
-  }
-}
-// Tiles of the one-call locate's scan (k_count_ctx kOne with U = 2 patterns per lane)
-constexpr uint64_t kLocTile = 2 * kBlk;
-static_assert(kLocTile == kLongRegion, "a tile is a region: one block's patterns");
-
-// position of BWT row `row` for the one-call locate: SA[row] (kPos 0) or the short walk
-template <int kPos>
-__device__ __forceinline__ uint64_t onepass_pos(const DevIndex& ix, const NodeTable& T, const OnePass& op,
-                                                uint64_t row) {
-  if constexpr (kPos == 0) return load_sa(op.sa, row);
-  else if constexpr (kPos == 1) return walk_position<WalkLine>(ix, T, row);
-  else return walk_position<WalkLineW>(ix, T, row);
-}
-
-// Exclusive scan over the block's U x kBlk values in pattern order (segment j holds the
-// patterns q0 + j kBlk, j < U): mine[j] = the offset of the lane's j-th value inside the
-// block, agg = the block's total.  Every thread of the block.
-template <int U>
-__device__ __forceinline__ void block_scan(const uint64_t* kc, uint64_t* mine, uint64_t& agg) {
-  constexpr int NW = kBlk / 64;
-  __shared__ uint64_t s_wsum[U][NW];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint64_t x[U];
-#pragma unroll
-  for (int j = 0; j < U; ++j) {
-    x[j] = kc[j];
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint64_t y = __shfl_up(x[j], d, 64);
-      if (lane >= d) x[j] += y;
-    }
-    if (lane == 63) s_wsum[j][wv] = x[j];
-  }
-  __syncthreads();
-  agg = 0;
-#pragma unroll
-  for (int j = 0; j < U; ++j) {
-    uint64_t before = agg;
-    for (int w2 = 0; w2 < NW; ++w2) {
-      if (w2 < wv) before += s_wsum[j][w2];
-      agg += s_wsum[j][w2];
-    }
-    mine[j] = before + x[j] - kc[j];
-  }
-}
-
-__device__ __forceinline__ void tile_total_add(const OnePass& op, uint64_t tile, uint64_t v) {
-  atomicAdd(reinterpret_cast<unsigned long long*>(op.tiles + tile), v);
-}
-
-// (1)'s tail: the lane's results.
-// A pattern reporting exactly one position gets it here, from the record already in the
-// lane (its first row: SA[row] - k for a context window), so its SA read overlaps the
-// other blocks' record reads instead of waiting for k_locate_emit; the record then holds
-// kLocStash | position and stands for the count 1 (no count is stored: 8 B per pattern).
-// (C4 Q_text: 99.6 % of the patterns.)
-constexpr uint64_t kLocStash = 1ull << 62;  // with bit 63 clear: not a window, not a row
-__device__ __forceinline__ bool loc_stashed(uint64_t r) { return (r >> 62) == 1; }
-// skip: bit j set = the lane's j-th pattern is k_locate_long's (routing): its count and record
-// are left for that kernel to write
-// kWaveTile (the barrier-free search, kPos 0): each wave adds its patterns' total to the tile
-// (zeroed at the block's start) instead of a block scan storing it, so no wave waits for the
-// block's others
-template <int U, int kPos = 0, bool kWaveTile = false>
-__device__ __forceinline__ void locate_split_store(const DevIndex& ix, const NodeTable& T, uint64_t npat,
-                                                   uint64_t tile, uint64_t q0, const uint64_t* kc,
-                                                   const uint64_t* kr, const OnePass& op, uint32_t skip = 0) {
-  const uint64_t n = ix.n;
-  uint64_t rs[U];
-  if constexpr (kWaveTile) {
-    uint64_t sum = 0;
-#pragma unroll
-    for (int j = 0; j < U; ++j) sum += kc[j];
-#pragma unroll
-    for (int dd = 32; dd >= 1; dd >>= 1) sum += __shfl_xor(sum, dd, 64);
-    if ((threadIdx.x & 63) == 0 && sum) tile_total_add(op, tile, sum);
-  } else {
-    uint64_t mine[U], agg;
-    block_scan<U>(kc, mine, agg);
-    if (threadIdx.x == 0) op.tiles[tile] = agg;
-  }
-  uint64_t row[U], adj[U];
-  bool one[U];
-#pragma unroll
-  for (int j = 0; j < U; ++j) {
-    const uint64_t q = q0 + (uint64_t)j * kBlk, s = kr[j];
-    rs[j] = s;
-    row[j] = s;
-    adj[j] = 0;
-    one[j] = q < npat && kc[j] == 1 && !loc_stashed(s);  // (not stashed by a locate record)
-    uint32_t rel;
-    if (one[j] && (s & kLocCtx)) loc_window(s, row[j], adj[j], rel);  // a window's only match: its first row
-  }
-  if constexpr (kPos == 0) {
-#pragma unroll
-    for (int j = 0; j < U; ++j)
-      if (one[j]) row[j] = load_sa(op.sa, row[j]);
-  } else {  // the lane's walks in lockstep: row[j] becomes the position
-    bool act[U];
-#pragma unroll
-    for (int j = 0; j < U; ++j) act[j] = one[j];
-    if constexpr (kWaveTile)  // (T is the global table: the walks' constants in registers)
-      walk_positions_k<std::conditional_t<kPos == 1, WalkLine, WalkLineW>, U>(ix, T, walk_consts(T), row, act);
-    else
-      walk_positions<std::conditional_t<kPos == 1, WalkLine, WalkLineW>, U>(ix, T, row, act);
-  }
-#pragma unroll
-  for (int j = 0; j < U; ++j)
-    if (one[j]) rs[j] = kLocStash | (row[j] >= adj[j] ? row[j] - adj[j] : row[j] + n - adj[j]);
-#pragma unroll
-  for (int j = 0; j < U; ++j) {
-    const uint64_t q = q0 + (uint64_t)j * kBlk;
-    if (q >= npat || ((skip >> j) & 1u)) continue;
-    if (!(kc[j] == 1 && loc_stashed(rs[j]))) {  // the count, and no stash standing for 1
-      if (op.cnt64) op.cnt64[q] = kc[j];
-      else op.cnt[q] = (uint32_t)kc[j];
-      if (loc_stashed(rs[j])) rs[j] = 0;  // (a limit of 0)
-    }
-    op.rec[q] = rs[j];
-  }
-}
-
-// (2): exclusive scan of the tile totals in place, one block; total -> *total_out.  The
-// tiles pass through LDS 16 k at a time (128 KB + padding: a workgroup may hold 160 KB), so
-// the global loads and stores are coalesced — the round-3 form gave each thread 32
-// consecutive tiles straight from memory (strided loads and stores: 28 us for C4's 24 k
-// tiles) — then each thread scans a contiguous run of 16 in registers and the block scans
-// the run totals.
-__device__ __forceinline__ uint32_t scan_pad(uint32_t i) { return i + (i >> 4); }  // LDS bank spread
-__global__ __launch_bounds__(1024) void k_scan_tiles(uint64_t* __restrict__ tiles, uint64_t ntiles,
-                                                     uint64_t* __restrict__ total_out) {
-  constexpr int kRun = 16;                     // tiles per thread per round
-  constexpr uint32_t kChunk = 1024u * kRun;    // tiles per round
-  __shared__ uint64_t s_v[kChunk + kChunk / kRun];
-  __shared__ uint64_t s_w[16];
-  __shared__ uint64_t s_carry;
-  const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  if (t == 0) s_carry = 0;
-  for (uint64_t b = 0; b < ntiles; b += kChunk) {
-#pragma unroll
-    for (int r = 0; r < kRun; ++r) {  // coalesced: tile b + r 1024 + t
-      const uint64_t i = b + (uint64_t)r * 1024 + t;
-      s_v[scan_pad(r * 1024u + t)] = i < ntiles ? tiles[i] : 0ull;
-    }
-    __syncthreads();
-    uint64_t v[kRun], run = 0;
-#pragma unroll
-    for (int r = 0; r < kRun; ++r) {  // the thread's run: tiles b + t kRun + r
-      v[r] = s_v[scan_pad(t * kRun + r)];
-      run += v[r];
-    }
-    uint64_t x = run;  // inclusive scan of the run totals over the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint64_t y = __shfl_up(x, d, 64);
-      if (lane >= (uint32_t)d) x += y;
-    }
-    if (lane == 63) s_w[wv] = x;
-    __syncthreads();
-    uint64_t pre = 0, tot = 0;
-#pragma unroll
-    for (int w2 = 0; w2 < 16; ++w2) {
-      if (w2 < (int)wv) pre += s_w[w2];
-      tot += s_w[w2];
-    }
-    uint64_t acc = s_carry + pre + x - run;
-#pragma unroll
-    for (int r = 0; r < kRun; ++r) {
-      s_v[scan_pad(t * kRun + r)] = acc;
-      acc += v[r];
-    }
-    __syncthreads();  // (every thread has read s_carry and s_w of this round)
-    if (t == 0) s_carry += tot;
-#pragma unroll
-    for (int r = 0; r < kRun; ++r) {
-      const uint64_t i = b + (uint64_t)r * 1024 + t;
-      if (i < ntiles) tiles[i] = s_v[scan_pad(r * 1024u + t)];
-    }
-    __syncthreads();  // before the next round's loads overwrite s_v and its scan reads s_carry
-  }
-  if (t == 0) *total_out = s_carry;
-}
-
-// the positions of a record's first c <= kLocSmall reported rows, minus the window's adj
-// (mod n), to out: SA reads kEmitRows at a time, in flight together
-// (the walk-line forms list their rows instead: emit_walk_lines)
-constexpr int kEmitRows = 4;
-template <int kPos>
-__device__ __forceinline__ void emit_rows(const DevIndex& ix, const NodeTable& T, const OnePass& op,
-                                          uint64_t* __restrict__ out, uint64_t c, LocRows rows) {
-  const uint64_t n = ix.n, adj = rows.adj;
-  for (uint64_t i = 0; i < c; i += kEmitRows) {
-    uint64_t row[kEmitRows];
-    bool act[kEmitRows];
-#pragma unroll
-    for (int u = 0; u < kEmitRows; ++u) {
-      act[u] = i + u < c;
-      row[u] = act[u] ? rows.next() : 0;
-    }
-    static_assert(kPos == 0, "walk-line indexes list their rows (emit_walk_lines)");
-#pragma unroll
-    for (int u = 0; u < kEmitRows; ++u)
-      if (act[u]) row[u] = load_sa(op.sa, row[u]);
-#pragma unroll
-    for (int u = 0; u < kEmitRows; ++u)
-      if (act[u]) st_out(out + i + u, row[u] >= adj ? row[u] - adj : row[u] + n - adj);
-  }
-}
-
-// (2'): the same scan over ceil(ntiles / 1024) blocks of 1024 tiles (one per thread): each
-// block publishes its total (one flag word), sums its predecessors' — every thread polls one
-// of them — and writes its tiles' exclusive prefixes; the last block writes the total.  The
-// blocks wait only on lower ones.  (Round 5: the one-block scan took 18 us of C4's 0.53-ms
-// one-call locate, its 24 k tiles passing through one CU.)  A block's place in the chain is
-// the order in which it STARTS (an atomic ticket, sflags[kScanMaxBlocks], zeroed by the
-// search kernel with the flags), not its blockIdx: a block only ever waits on blocks that
-// are already running, whatever order the dispatcher picks (with other streams'
-// kernels sharing the CUs, blockIdx order is not guaranteed).
-__global__ __launch_bounds__(kScanBlock) void k_scan_chained(uint64_t* __restrict__ tiles, uint64_t ntiles,
-                                                             uint64_t* __restrict__ total_out,
-                                                             unsigned long long* __restrict__ sflags) {
-  __shared__ uint64_t s_w[kScanBlock / 64];
-  __shared__ uint64_t s_p[kScanBlock / 64];
-  __shared__ uint32_t s_id;
-  const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  if (t == 0) s_id = (uint32_t)atomicAdd(sflags + kScanMaxBlocks, 1ull);
-  __syncthreads();
-  const uint32_t bid = s_id;
-  const uint64_t i = (uint64_t)bid * kScanBlock + t;
-  const uint64_t v = i < ntiles ? tiles[i] : 0ull;
-  uint64_t x = v;  // inclusive scan over the wave, then the block
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t y = __shfl_up(x, d, 64);
-    if (lane >= (uint32_t)d) x += y;
-  }
-  if (lane == 63) s_w[wv] = x;
-  __syncthreads();
-  uint64_t pre = 0, agg = 0;
-#pragma unroll
-  for (int w2 = 0; w2 < (int)(kScanBlock / 64); ++w2) {
-    if (w2 < (int)wv) pre += s_w[w2];
-    agg += s_w[w2];
-  }
-  if (t == 0)
-    __hip_atomic_store(sflags + bid, (1ull << 63) | agg, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-  uint64_t p = 0;  // predecessor t's total
-  if (t < bid) {
-    unsigned long long f;
-    do {
-      f = __hip_atomic_load(sflags + t, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-    } while (!(f >> 63));
-    p = f & ~(1ull << 63);
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) p += __shfl_xor(p, d, 64);
-  if (lane == 0) s_p[wv] = p;
-  __syncthreads();
-  uint64_t base = 0;
-#pragma unroll
-  for (int w2 = 0; w2 < (int)(kScanBlock / 64); ++w2) base += s_p[w2];
-  if (i < ntiles) tiles[i] = base + pre + x - v;
-  if (bid == gridDim.x - 1 && t == 0) *total_out = base + agg;
-}
-
-// (3) on walk-line indexes: offsets, the stashed positions, and the rows of every pattern
-// with 2..kLocSmall positions listed for k_locate_walks in the tile's slots (a block scan
-// places them: no atomic) instead of walked here — a lane walking its pattern's positions
-// one after another kept its wave, and the emit, waiting (C5: the emit 360 us per 12.5 M
-// 20-mers; 617 with four walks of a lane in lockstep; 1,156 with one global list counter,
-// 98 k same-address atomics, profiles/r05/r05x, r05y).  A pattern past the tile's kLocTile
-// slots is walked here (its slots below the limit marked void).
-template <int U, int kPos>
-__device__ __forceinline__ void emit_walk_lines(const DevIndex& ix, NodeTable& T, uint64_t npat, uint64_t tile,
-                                                uint64_t q0, const uint64_t* kc, const uint64_t* kr,
-                                                const uint64_t* mine, uint64_t base, const OnePass& op) {
-  using W = std::conditional_t<kPos == 1, WalkLine, WalkLineW>;
-  const uint64_t n = ix.n;
-  uint64_t nl[U], tot = 0;
-#pragma unroll
-  for (int j = 0; j < U; ++j) {
-    const uint64_t q = q0 + (uint64_t)j * kBlk, a = base + mine[j], c = kc[j], s = kr[j];
-    nl[j] = 0;
-    if (q >= npat) continue;
-    st_out(op.out_offs + q, a);
-    if (!c || a + c > op.cap) continue;  // capacity short: the caller sees the total
-    if (loc_stashed(s)) {
-      st_out(op.out_pos + a, s & (kLocStash - 1));
-    } else if ((s & kLocCtx) || c <= kLocSmall) {
-      nl[j] = c;
-    } else {
-      const unsigned long long e = atomicAdd(op.nwide, 1ull);
-      if (e < op.wide_cap) {
-        op.wide[2 * e] = q;
-        op.wide[2 * e + 1] = s;
-      }
-    }
-    tot += nl[j];
-  }
-  // the lane's place among the tile's listed rows
-  uint64_t at, all;
-  block_scan<1>(&tot, &at, all);
-  if (threadIdx.x == 0) op.wcnt[tile] = (uint32_t)(all < kLocTile ? all : kLocTile);
-  uint64_t* const slots = op.walks + 2 * tile * kLocTile;
-  uint32_t fb = 0;  // patterns walked here (past the tile's slots)
-#pragma unroll
-  for (int j = 0; j < U; ++j) {
-    if (!nl[j]) continue;
-    const uint64_t a = base + mine[j], s = kr[j], c = nl[j];
-    const bool fits = at + c <= kLocTile;
-    fb |= (uint32_t)!fits << j;
-    LocRows rows = LocRows::of(s);
-    for (uint64_t i = 0; i < c; ++i, ++at) {
-      const uint64_t row = rows.next();
-      if (at >= kLocTile) continue;
-      slots[2 * at] = fits ? a + i : ~0ull;  // (a void slot: k_locate_walks skips it)
-      slots[2 * at + 1] = row | (rows.adj << kWalkAdjShift);
-    }
-  }
-  if (__syncthreads_or(fb != 0)) {
-    load_table(T, ix.table);
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      if (!((fb >> j) & 1u)) continue;
-      const uint64_t a = base + mine[j];
-      LocRows rows = LocRows::of(kr[j]);
-      const uint64_t adj = rows.adj;
-      for (uint64_t i = 0; i < nl[j]; ++i) {
-        const uint64_t p = walk_position<W>(ix, T, rows.next());
-        st_out(op.out_pos + a + i, p >= adj ? p - adj : p + n - adj);
-      }
-    }
-  }
-}
-
-// (3') the listed walks (emit_walk_lines): block b takes tiles b, b + grid, ... (one per
-// thread: the grid is at least tiles / kBlk), their slots flattened, two per lane in lockstep
-template <int kPos>
-__global__ __launch_bounds__(kBlk) void k_locate_walks(DevIndex ix, OnePass op, uint64_t ntiles) {
-  using W = std::conditional_t<kPos == 1, WalkLine, WalkLineW>;
-  static_assert(kBlk == 256, "the tile lookup below searches 256 tiles in 8 steps");
-  __shared__ NodeTable T;
-  __shared__ uint32_t s_off[kBlk + 1];
-  __shared__ uint32_t s_w[kBlk / 64];
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const uint64_t mt = blockIdx.x + (uint64_t)threadIdx.x * gridDim.x;
-  const uint32_t c = mt < ntiles ? op.wcnt[mt] : 0u;
-  uint32_t x = c;  // exclusive scan of the tiles' counts over the block
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d, 64);
-    if (lane >= (uint32_t)d) x += y;
-  }
-  if (lane == 63) s_w[wv] = x;
-  __syncthreads();
-  uint32_t pre = 0, tot = 0;
-#pragma unroll
-  for (int w2 = 0; w2 < (int)(kBlk / 64); ++w2) {
-    if (w2 < (int)wv) pre += s_w[w2];
-    tot += s_w[w2];
-  }
-  s_off[threadIdx.x] = pre + x - c;
-  if (threadIdx.x == 0) s_off[kBlk] = tot;
-  if (tot == 0) return;  // uniform: nothing listed in the block's tiles
-  load_table(T, ix.table);
-  __syncthreads();
-  const uint64_t n = ix.n;
-  for (uint32_t e0 = 0; e0 < tot; e0 += 2 * kBlk) {
-    uint64_t row[2], adj[2], idx[2];
-    bool act[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const uint32_t ee = e0 + threadIdx.x + h * kBlk;
-      const uint32_t e = ee < tot ? ee : 0u;
-      uint32_t lo = 0, hi = kBlk;  // s_off[lo] <= e < s_off[hi] (empty tiles share offsets)
-#pragma unroll
-      for (int it = 0; it < 8; ++it) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (s_off[mid] <= e) lo = mid;
-        else hi = mid;
-      }
-      const uint64_t* sl = op.walks + 2 * ((blockIdx.x + (uint64_t)lo * gridDim.x) * kLocTile + (e - s_off[lo]));
-      idx[h] = ee < tot ? sl[0] : ~0ull;
-      const uint64_t v = ee < tot ? sl[1] : 0;
-      act[h] = idx[h] != ~0ull;
-      row[h] = v & kWalkRowMask;
-      adj[h] = v >> kWalkAdjShift;
-    }
-    bool w[2] = {act[0], act[1]};
-    walk_positions<W, 2>(ix, T, row, w);
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-      if (act[h]) st_out(op.out_pos + idx[h], row[h] >= adj[h] ? row[h] - adj[h] : row[h] + n - adj[h]);
-  }
-}
-
-// (3): offsets and positions of tile blockIdx.x (round 5: a pattern whose record is a stashed
-// position has no count stored: 8 B read per pattern instead of 12.  Tried in round 5 to drop
-// the scan kernel: a decoupled look-back over the tiles — its frontier moves 64 tiles per L2
-// round trip, 0.63 against 0.53 ms per C4 call — 1024 blocks taking a share of the tiles each
-// with a running base — 4 waves per SIMD and a serial tile loop, the emit 125 against 67 us
-// — share totals added by the search kernel's waves — same-address atomics of
-// neighbouring blocks, the search 426 -> 615 us — and two tiles per block, 4 patterns per
-// lane with both tiles' records in flight before one scan: 0.520 -> 0.536 ms per call,
-// profiles/r05/r05aj.)
-template <int U, int kPos = 0>
-__global__ __launch_bounds__(kBlk) void k_locate_emit(DevIndex ix, uint64_t npat, OnePass op) {
-  __shared__ NodeTable T;  // kPos: the walks' C[] and codes (a pattern past walk_cap)
-  const uint64_t tile = blockIdx.x;
-  const uint64_t q0 = tile * (uint64_t)(kBlk * U) + threadIdx.x;
-  uint64_t kc[U], kr[U], mine[U], agg;
-  const uint64_t base = op.tiles[tile];  // (issued with the records: its latency overlaps theirs)
-#pragma unroll
-  for (int j = 0; j < U; ++j) {
-    const uint64_t q = q0 + (uint64_t)j * kBlk;
-    // (read once: non-temporal loads, 0.560 -> 0.554 ms per call over three A/B rounds,
-    // profiles/r04/ab_lib_r04af.jsonl); the count only where the record is no stash
-    kr[j] = q < npat ? __builtin_nontemporal_load(op.rec + q) : 0;
-    kc[j] = q >= npat ? 0 : loc_stashed(kr[j]) ? 1
-          : (op.cnt64 ? __builtin_nontemporal_load(op.cnt64 + q) : __builtin_nontemporal_load(op.cnt + q));
-  }
-  if constexpr (kPos != 0) {
-    block_scan<U>(kc, mine, agg);
-    emit_walk_lines<U, kPos>(ix, T, npat, tile, q0, kc, kr, mine, base, op);
-  } else {
-    block_scan<U>(kc, mine, agg);
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      const uint64_t q = q0 + (uint64_t)j * kBlk;
-      if (q >= npat) continue;
-      const uint64_t a = base + mine[j], c = kc[j];
-      st_out(op.out_offs + q, a);
-      if (!c || a + c > op.cap) continue;  // capacity short: the caller sees the total
-      const uint64_t s = kr[j];
-      if (loc_stashed(s)) {  // kLocStash: the one position, read by the search kernel
-        st_out(op.out_pos + a, s & (kLocStash - 1));
-      } else if (s & kLocCtx) {  // a window k characters before the end (k_locate_sa)
-        emit_rows<kPos>(ix, T, op, op.out_pos + a, c, LocRows::of(s));
-      } else if (c <= kLocSmall) {
-        emit_rows<kPos>(ix, T, op, op.out_pos + a, c, LocRows(s));
-      } else {
-        const unsigned long long e = atomicAdd(op.nwide, 1ull);
-        if (e < op.wide_cap) {
-          op.wide[2 * e] = q;
-          op.wide[2 * e + 1] = s;
-        }
-      }
-    }
-  }
-}
-
-// the ranges over kLocSmall rows: a block per range
-template <int kPos = 0>
-__global__ __launch_bounds__(kBlk) void k_locate_emit_wide(DevIndex ix, OnePass op, const uint64_t* __restrict__ offs,
-                                                           uint64_t* __restrict__ out) {
-  __shared__ NodeTable T;
-  const uint64_t nw = *op.nwide < op.wide_cap ? *op.nwide : op.wide_cap;
-  if (blockIdx.x >= nw) return;  // uniform over the block
-  if constexpr (kPos != 0) {
-    load_table(T, ix.table);
-    __syncthreads();
-  }
-  for (uint64_t e = blockIdx.x; e < nw; e += gridDim.x) {
-    const uint64_t q = op.wide[2 * e], s = op.wide[2 * e + 1], a = offs[q], c = offs[q + 1] - a;
-    for (uint64_t j = threadIdx.x; j < c; j += blockDim.x) st_out(out + a + j, onepass_pos<kPos>(ix, T, op, s + j));
-  }
-}
-
 // The lanes' patterns j with bit j of `m` set into the wave's slot of a LongList list (their
 // offsets inside the block's region, in ballot order) and their number into cnt[slot] (0
 // when none); returns that number (uniform).  Every lane of the wave, in uniform control flow.
@@ -775,15 +253,13 @@ void k_count_ctx(DevIndex ix, const uint8_t* __restrict__ pats,
   static_assert(!kSkipLong || U * kBlk == kLongRegion, "a block's waves list one region's slots");
   if (threadIdx.x < 256)
     cmap[threadIdx.x] = (uint16_t)(ix.table->code[threadIdx.x] | (ix.table->occ_code[threadIdx.x] << 8));
-  if (kOne && threadIdx.x == 0) {
+  if constexpr (kOne) {
     // the block's tile, which its waves add to after the barrier, and the call's wide-range
-    // counter: no memset launch.  The stores are acknowledged by the L2 (where the waves'
-    // atomics land) before this wave reaches the barrier.
-    op.tiles[blockIdx.x] = 0;
-    if (blockIdx.x == 0) *op.nwide = 0;
-    if (op.sflags && blockIdx.x < kScanMaxBlocks) op.sflags[blockIdx.x] = 0;
-    if (op.sflags && blockIdx.x == 0) op.sflags[kScanMaxBlocks] = 0;  // the chained scan's ticket
-    __builtin_amdgcn_s_waitcnt(0);
+    // counter, flags and ticket (onepass_zero): no memset launch.  The stores are acknowledged
+    // by the L2 (where the waves' atomics land) before this wave reaches the barrier.
+    if (threadIdx.x == 0) op.tiles[blockIdx.x] = 0;
+    onepass_zero(op);
+    if (threadIdx.x == 0) __builtin_amdgcn_s_waitcnt(0);
   }
   // the list kernels' retire word (list_retire) is this call's from here on, whatever the
   // caller's memory held: the list kernels run after this kernel in stream order, and no
@@ -1050,7 +526,7 @@ void k_count_ctx(DevIndex ix, const uint8_t* __restrict__ pats,
         }
         st[j] = 0;
         res[j] = mt;
-        if (mt) rv[j] = kLocStash | (mp >= k[j] ? mp - k[j] : mp + ix.n - k[j]);
+        if (mt) rv[j] = kLocStash | pos_back(mp, k[j], ix.n);
       }
     } else {
     // (B0) the locate records: no match, or one matching row whose SA value the record holds,
@@ -1080,7 +556,7 @@ void k_count_ctx(DevIndex ix, const uint8_t* __restrict__ pats,
       res[j] = mm ? 1u : 0u;
       if (mm) {
         const uint64_t v = mm == 1u ? a.x : mm == 2u ? a.y : a.z;
-        rv[j] = kLocStash | (v >= j2 ? v - j2 : v + ix.n - j2);
+        rv[j] = kLocStash | pos_back(v, j2, ix.n);
       }
     }
     }
@@ -1736,91 +1212,32 @@ __device__ __forceinline__ uint32_t slot_count(const uint32_t* cnt, uint64_t npa
 
 template <class T, class F>
 __device__ __forceinline__ uint32_t list_for_each(const T* __restrict__ list, uint32_t c, F&& f) {
-  static_assert(kBlk == 256, "the slot lookup below searches 256 slots in 8 steps");  // 
   __shared__ uint32_t s_off[kBlk + 1];
   __shared__ uint32_t s_w[kBlk / 64];
-  // exclusive scan of the counts over the block
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t x = c;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d, 64);
-    if (lane >= (uint32_t)d) x += y;
-  }
-  if (lane == 63) s_w[wv] = x;
+  const uint32_t tot = slot_offsets(c, s_off, s_w);
   __syncthreads();
-  uint32_t pre = 0, tot = 0;
-#pragma unroll
-  for (int w2 = 0; w2 < (int)(kBlk / 64); ++w2) {
-    if (w2 < (int)wv) pre += s_w[w2];
-    tot += s_w[w2];
-  }
-  s_off[threadIdx.x] = pre + x - c;
-  if (threadIdx.x == 0) s_off[kBlk] = tot;
-  __syncthreads();
-  for (uint32_t e0 = 0; e0 < tot; e0 += kBlk) {
-    const uint32_t e = e0 + threadIdx.x < tot ? e0 + threadIdx.x : 0u;
-    // the slot holding entry e: the last t with s_off[t] <= e (empty slots share offsets)
-    uint32_t lo = 0, hi = kBlk;  // s_off[lo] <= e < s_off[hi]
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (s_off[mid] <= e) lo = mid;
-      else hi = mid;
-    }
-    const uint64_t s2 = blockIdx.x + (uint64_t)lo * gridDim.x;
-    const uint64_t q = s2 / kSlotsPerRegion * kLongRegion + (list[s2 * kLongSlot + (e - s_off[lo])] & (kLongRegion - 1));
-    f(q, e0 + threadIdx.x < tot);
-  }
+  slot_entries<1>(s_off, tot, [&](const uint32_t* owner, const uint32_t* place, const bool* live) {
+    const uint64_t s2 = blockIdx.x + (uint64_t)owner[0] * gridDim.x;
+    f(s2 / kSlotsPerRegion * kLongRegion + (list[s2 * kLongSlot + place[0]] & (kLongRegion - 1)), live[0]);
+  });
   return tot;
 }
 
 // list_for_each with two entries per thread and round (e and e + kBlk of 2 kBlk): f(q, act)
-// with q[2], act[2], the whole block in lockstep
+// with q[2] (the entries' indices in the list: their slot's base + their place), act[2], the
+// whole block in lockstep
 template <class F>
 __device__ __forceinline__ uint32_t list_for_each2(uint32_t c, F&& f) {
-  static_assert(kBlk == 256, "the slot lookup below searches 256 slots in 8 steps");
   __shared__ uint32_t s_off2[kBlk + 1];
   __shared__ uint32_t s_w2[kBlk / 64];
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t x = c;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d, 64);
-    if (lane >= (uint32_t)d) x += y;
-  }
-  if (lane == 63) s_w2[wv] = x;
+  const uint32_t tot = slot_offsets(c, s_off2, s_w2);
   __syncthreads();
-  uint32_t pre = 0, tot = 0;
-#pragma unroll
-  for (int w2 = 0; w2 < (int)(kBlk / 64); ++w2) {
-    if (w2 < (int)wv) pre += s_w2[w2];
-    tot += s_w2[w2];
-  }
-  s_off2[threadIdx.x] = pre + x - c;
-  if (threadIdx.x == 0) s_off2[kBlk] = tot;
-  __syncthreads();
-  for (uint32_t e0 = 0; e0 < tot; e0 += 2 * kBlk) {
+  slot_entries<2>(s_off2, tot, [&](const uint32_t* owner, const uint32_t* place, const bool* live) {
     uint64_t q[2];
-    bool act[2];
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const uint32_t ee = e0 + threadIdx.x + h * kBlk;
-      act[h] = ee < tot;
-      const uint32_t e = act[h] ? ee : 0u;
-      uint32_t lo = 0, hi = kBlk;  // s_off2[lo] <= e < s_off2[hi]
-#pragma unroll
-      for (int it = 0; it < 8; ++it) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (s_off2[mid] <= e) lo = mid;
-        else hi = mid;
-      }
-      const uint64_t s2 = blockIdx.x + (uint64_t)lo * gridDim.x;
-      // (the entry's index in the list: its slot's base + its place)
-      q[h] = s2 * kLongSlot + (e - s_off2[lo]);
-    }
-    f(q, act);
-  }
+    for (int h = 0; h < 2; ++h) q[h] = (blockIdx.x + (uint64_t)owner[h] * gridDim.x) * kLongSlot + place[h];
+    f(q, live);
+  });
   return tot;
 }
 
@@ -2053,7 +1470,7 @@ __device__ __forceinline__ void count_long_one(const DevIndex& ix, const uint8_t
       cand &= cand - 1;
       uint64_t p, wsteps = 0;
       if constexpr (kWalk != 0) {
-        using WL = std::conditional_t<kWalk == 1, WalkLine, WalkLineW>;
+        using WL = WalkLineOf<kWalk>;
         if constexpr (kBytes) {  // (the twin counts the walk's lines)
           p = walk_one<WL, false>(ix, *ix.table, base + i, wsteps);
         } else {
@@ -2065,7 +1482,7 @@ __device__ __forceinline__ void count_long_one(const DevIndex& ix, const uint8_t
       } else {
         p = load_sa(ix.vsa, base + i);
       }
-      const uint64_t wq = p >= k ? p - k : p + n - k;
+      const uint64_t wq = pos_back(p, k, n);
       if constexpr (kBytes) {  // the SA sector (walk: its lines and the sample), then the window's words
         constexpr uint64_t C = 32ull * kLongPW;
         by += kWalk ? 32 * (wsteps + 1) + 8 : 32;
@@ -2146,25 +1563,6 @@ __global__ __launch_bounds__(kBlk) __attribute__((amdgpu_waves_per_eu(kList ? 4 
 }
 
 
-// Adds each lane's kc (0: nothing) to op.tiles[tile]: one atomic per distinct tile of the
-// wave (a list launch's wave holds one or two slots' patterns, so one or two tiles; a
-// pattern-per-lane atomic puts 512 same-address atomics on every tile: C4 150-mer locate
-// 2.1 -> 3.4 ms).  Every lane of the wave, in uniform control flow.
-__device__ __forceinline__ void wave_tile_add(const OnePass& op, uint64_t tile, uint64_t kc) {
-  const uint32_t lane = threadIdx.x & 63;
-  uint64_t pend = __ballot(kc != 0);
-  while (pend) {
-    const uint32_t l = (uint32_t)__ffsll((unsigned long long)pend) - 1u;
-    const uint64_t t = __shfl(tile, (int)l, 64);
-    const bool in = kc != 0 && tile == t;
-    uint64_t s = in ? kc : 0;
-#pragma unroll
-    for (int dd = 32; dd >= 1; dd >>= 1) s += __shfl_xor(s, dd, 64);
-    if (lane == l) tile_total_add(op, t, s);
-    pend &= ~__ballot(in);
-  }
-}
-
 // The long-pattern search for the one-call locate (launch_locate_onepass over full-SA
 // indexes: CS_Q_LONG, host batches of long patterns, and the long patterns the staged kernel
 // lists): k_count_long's stages, then per pattern min(count, limit) and its record for
@@ -2197,6 +1595,8 @@ __device__ __forceinline__ void locate_long_one(const DevIndex& ix, const uint8_
       for (uint32_t c = cand; c; c &= c - 1) {
         const uint32_t i = (uint32_t)__ffs(c) - 1u;
         const uint64_t p = load_sa(ix.vsa, base + i);
+        // (pos_back's text, written out: through the helper the unrouted forms take 97 VGPRs
+        // instead of 96 and lose a wave per SIMD)
         const uint64_t wq = p >= k ? p - k : p + n - k;
         if (window_eq_packed<kV16 == 3>(ix, pc, pats + o0, wq, L, rare)) {
           if (!mm) p0 = wq;
@@ -2413,7 +1813,7 @@ __device__ __forceinline__ uint64_t locate_miss_one(const DevIndex& ix, const No
     uint32_t rel;
     if (rv & kLocCtx) loc_window(rv, row, adj, rel);
     const uint64_t p = load_sa(sa, row);
-    rv = kLocStash | (p >= adj ? p - adj : p + ix.n - adj);
+    rv = kLocStash | pos_back(p, adj, ix.n);
   }
   rec = rv;
   return kc;
@@ -3433,46 +2833,12 @@ cs_status launch_locrec_hits(const cs_fm_index* h, const uint8_t* d_pats, const 
   return CS_OK;
 }
 
-// Batch locate in one call (OnePass above): occurrence lines with a prefix table, left
+// Batch locate in one call (fm_locate.hpp): the route decisions, the search launches, then
+// the finish (fm_locate.hip).  Occurrence lines with a prefix table, left
 // contexts and the full suffix array (C2, C4).  *done = false when the index has another
 // shape (the caller runs the two phases).  Writes d_out_offs (npat + 1) and, when the
 // total fits `cap`, every position; synchronises `st` for *total.  CS_QT_NO_ONEPASS
 // (CS_FM_LOCATE_ONEPASS=0) turns it off.
-// The call's buffers (the lists, then per pattern its count and record, the tiles, the wide
-// ranges) in the caller's workspace when it holds locate_workspace_bytes(npat), else in one
-// stream-ordered allocation.
-// (+ on walk-line indexes the walk list: kLocTile (output index, row) pairs per tile and the
-// tiles' counts)
-// Where each part sits (byte offsets from the buffers' start, after the lists) and the total:
-// the one description the workspace sizes and launch_locate_onepass's pointers share.
-struct LocateLayout {
-  uint64_t ntiles;  // tiles of kLocTile patterns
-  uint64_t rec, tiles, nwide, wide, counts, wcnt, walks, sflags, bytes;
-  LocateLayout(const cs_fm_index* h, uint64_t npat, uint64_t wide_cap) {
-    ntiles = (npat + kLocTile - 1) / kLocTile;
-    const uint64_t cb = h->wide ? 8 : 4;  // count bytes (a wide index's counts pass 2^32)
-    const bool walk = !h->d_sa;           // a walk-line index: the walk list
-    rec = 0;                                              // a record per pattern, 8 B
-    tiles = rec + npat * 8;                               // a total per tile, 8 B
-    nwide = tiles + ntiles * 8;                           // the wide ranges' counter, 8 B
-    wide = nwide + 8;                                     // wide_cap wide ranges, 16 B each
-    counts = wide + wide_cap * 16;                        // a count per pattern, cb bytes
-    wcnt = counts + ((npat * cb + 7) & ~7ull);            // the tiles' walk counts, u32
-    walks = wcnt + (walk ? (ntiles * 4 + 7) & ~7ull : 0);  // kLocTile 16-B walk slots per tile
-    sflags = walks + (walk ? ntiles * kLocTile * 16 : 0);  // the chained scan's flags and ticket
-    bytes = sflags + (kScanMaxBlocks + 1) * 8;
-  }
-};
-uint64_t locate_walk_bytes(const cs_fm_index* h, uint64_t npat) {
-  const LocateLayout L(h, npat, npat);
-  return L.sflags - L.wcnt;
-}
-uint64_t locate_lo_bytes(const cs_fm_index* h, uint64_t npat, uint64_t wide_cap) {
-  return LocateLayout(h, npat, wide_cap).bytes;
-}
-uint64_t locate_workspace_bytes(const cs_fm_index* h, uint64_t npat) {
-  return LongBufs::bytes(npat, false) + locate_lo_bytes(h, npat, npat);
-}
 cs_status launch_locate_onepass(const cs_fm_index* h, const uint8_t* d_pats, const uint64_t* d_offs,
                                 uint64_t npat, uint64_t limit, uint64_t* d_out_offs,
                                 uint64_t* d_out_pos, uint64_t cap, uint64_t* total, hipStream_t st,
@@ -3483,7 +2849,7 @@ cs_status launch_locate_onepass(const cs_fm_index* h, const uint8_t* d_pats, con
   DevIndex ix = h->dev();
   if (flags & CS_Q_NO_LOC_RECORDS) ix.lrec = nullptr;
   // positions from the full SA (narrow), or by the short walk over walk lines with
-  // text-position marks (OnePass above); CS_QT_ONEPASS_SA (CS_FM_LOCATE_ONEPASS=2): the full
+  // text-position marks (fm_locate.hpp); CS_QT_ONEPASS_SA (CS_FM_LOCATE_ONEPASS=2): the full
   // SA only (a walk index takes the two phases)
   const bool by_sa = h->d_sa && !h->wide;
   const bool by_walk = !h->d_sa && h->d_walk && h->d_wssa && h->walk_marks == 2 && !(flags & CS_QT_ONEPASS_SA);
@@ -3529,38 +2895,13 @@ cs_status launch_locate_onepass(const cs_fm_index* h, const uint8_t* d_pats, con
   // stream-ordered allocation per call without a workspace, not two)
   const bool lists = long_only || routed || defer;
   const uint64_t lb_bytes = lists ? LongBufs::bytes(npat, long_only) : 0;
-  const LocateLayout L(h, npat, wide_cap);
-  const uint64_t lo = L.bytes;
-  const bool use_ws = work.p && work.bytes >= LongBufs::bytes(npat, false) + lo;
-  StreamBuf wsb;
-  uint8_t* base;
-  uint64_t lo_at;
-  if (use_ws) {
-    base = static_cast<uint8_t*>(work.p);
-    lo_at = LongBufs::bytes(npat, false);  // (the workspace's lists sit where a count's do)
-  } else {
-    FMX_HIP(wsb.alloc(lb_bytes + lo, st));
-    base = wsb.as<uint8_t>();
-    lo_at = lb_bytes;
-  }
-  OnePass op;
-  uint8_t* const lp = base + lo_at;
-  op.rec = reinterpret_cast<uint64_t*>(lp + L.rec);
-  op.tiles = reinterpret_cast<uint64_t*>(lp + L.tiles);
-  op.nwide = reinterpret_cast<unsigned long long*>(lp + L.nwide);
-  op.wide = reinterpret_cast<uint64_t*>(lp + L.wide);
-  if (h->wide) op.cnt64 = reinterpret_cast<uint64_t*>(lp + L.counts);
-  else op.cnt = reinterpret_cast<uint32_t*>(lp + L.counts);
-  if (kpos != 0) {  // (walk-line indexes)
-    op.wcnt = reinterpret_cast<uint32_t*>(lp + L.wcnt);
-    op.walks = reinterpret_cast<uint64_t*>(lp + L.walks);
-  }
-  op.sflags = reinterpret_cast<unsigned long long*>(lp + L.sflags);
-  op.sa = static_cast<const uint32_t*>(h->d_sa);
+  LocateBufs bufs;
+  cs_status bs = locate_buffers(h, npat, wide_cap, LongBufs::bytes(npat, false), lb_bytes, work, st, bufs);
+  if (bs != CS_OK) return bs;
+  OnePass& op = bufs.op;
   op.out_offs = d_out_offs;
   op.out_pos = d_out_pos;
   op.cap = d_out_pos ? cap : 0;
-  op.wide_cap = wide_cap;
   op.defer = defer ? 1u : 0u;
   // the search kernel's blocks zero their tiles (and block 0 the wide-range counter); a
   // CS_Q_LONG call, which runs no search kernel, zeroes them here
@@ -3570,7 +2911,7 @@ cs_status launch_locate_onepass(const cs_fm_index* h, const uint8_t* d_pats, con
   }
   LongBufs lb;
   if (lists) {
-    cs_status ls = lb.alloc(npat, long_only, st, base, !use_ws);
+    cs_status ls = lb.alloc(npat, long_only, st, bufs.base, !bufs.in_ws);
     if (ls != CS_OK) return ls;
   }
   const CountOut co{nullptr, nullptr, nullptr, 0, 8};
@@ -3616,25 +2957,7 @@ cs_status launch_locate_onepass(const cs_fm_index* h, const uint8_t* d_pats, con
     k_locate_list<<<long_list_grid(npat, h->list_grid), kBlk, 0, st>>>(ix, d_pats, d_offs, npat, limit, op, lb.ll);
     FMX_HIP(hipGetLastError());
   }
-  // (k_locate_walks: 4 blocks per CU, and one tile per thread)
-  const unsigned walk_grid = (unsigned)std::max<uint64_t>(list_blocks_per_device(), (tiles + kBlk - 1) / kBlk);
-  // the chained scan (a block per 1024 tiles) while its look-back fits a block, else one block
-  const uint64_t sblocks = (tiles + kScanBlock - 1) / kScanBlock;
-  if (sblocks <= kScanMaxBlocks)
-    k_scan_chained<<<(unsigned)sblocks, kScanBlock, 0, st>>>(op.tiles, tiles, d_out_offs + npat, op.sflags);
-  else
-    k_scan_tiles<<<1, 1024, 0, st>>>(op.tiles, tiles, d_out_offs + npat);
-  FMX_HIP(hipGetLastError());
-  // kPos: positions from the full SA (0), or by the walk over narrow (1) / wide (2) walk lines
-  with_int<0, 1, 2>(kpos, [&](auto kPos) {
-    k_locate_emit<U, kPos><<<(unsigned)tiles, kBlk, 0, st>>>(ix, npat, op);
-    if constexpr (kPos != 0) k_locate_walks<kPos><<<walk_grid, kBlk, 0, st>>>(ix, op, tiles);
-    k_locate_emit_wide<kPos><<<1024, kBlk, 0, st>>>(ix, op, d_out_offs, d_out_pos);
-  });
-  FMX_HIP(hipGetLastError());
-  FMX_HIP(hipMemcpyAsync(total, d_out_offs + npat, 8, hipMemcpyDeviceToHost, st));
-  FMX_HIP(hipStreamSynchronize(st));
-  return CS_OK;
+  return launch_locate_finish(ix, npat, tiles, kpos, op, total, st);
 }
 
 cs_status launch_locate_ranges(const cs_fm_index* h, const uint8_t* d_pats,

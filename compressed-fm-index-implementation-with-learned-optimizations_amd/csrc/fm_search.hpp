@@ -709,6 +709,84 @@ __device__ __forceinline__ void st_out(T* p, T v) {
   __builtin_nontemporal_store(v, p);
 }
 
+// ---- block scans ----
+// Inclusive scan of one value per lane over the wave, written over the value.
+template <class V>
+__device__ __forceinline__ void wave_scan_incl(V& x) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const V y = __shfl_up(x, d, 64);
+    if (lane >= d) x += y;
+  }
+}
+// The waves' totals (s_w[NW], stored by each wave's lane 63 before a barrier): the sum of the
+// waves below the thread's, and tot = the sum of all.
+template <class V, int NW>
+__device__ __forceinline__ V waves_below(const V* s_w, V& tot) {
+  const int wv = threadIdx.x >> 6;
+  V pre = 0;
+  tot = 0;
+#pragma unroll
+  for (int w2 = 0; w2 < NW; ++w2) {
+    if (w2 < wv) pre += s_w[w2];
+    tot += s_w[w2];
+  }
+  return pre;
+}
+// Exclusive scan of one value per thread over a block of NW waves: returns the sum of the
+// values of the threads below, tot = the block's total.  s_w: NW values of LDS, the caller's
+// (free again after the caller's next barrier).  Every thread of the block; one barrier.
+template <class V, int NW>
+__device__ __forceinline__ V block_scan_excl(V v, V* s_w, V& tot) {
+  V x = v;
+  wave_scan_incl(x);
+  if ((threadIdx.x & 63) == 63) s_w[threadIdx.x >> 6] = x;
+  __syncthreads();
+  return waves_below<V, NW>(s_w, tot) + x - v;
+}
+
+// ---- the entries of a block's slots ----
+// Each thread of the block owns a slot holding c entries (a list slot, a tile's walk slots).
+// slot_offsets: the exclusive offsets of the kBlk counts into s_off[kBlk + 1] (s_off[kBlk] =
+// their total, returned, uniform); the caller puts a barrier between it and slot_entries.
+// slot_entries<H>: the tot entries flattened, H kBlk per round, entry e0 + threadIdx.x +
+// h kBlk the thread's h-th, so every lane has one while the block has any: f(owner, place,
+// live) — owner[h] the thread whose slot holds the entry, place[h] its index inside that slot,
+// live[h] false past the last entry (the lane then gets the block's first entry) — runs with
+// the whole block in lockstep, so f may use wave collectives and barriers.
+__device__ __forceinline__ uint32_t slot_offsets(uint32_t c, uint32_t* s_off, uint32_t* s_w) {
+  uint32_t tot;
+  s_off[threadIdx.x] = block_scan_excl<uint32_t, kBlk / 64>(c, s_w, tot);
+  if (threadIdx.x == 0) s_off[kBlk] = tot;
+  return tot;
+}
+template <int H, class F>
+__device__ __forceinline__ void slot_entries(const uint32_t* s_off, uint32_t tot, F&& f) {
+  static_assert(kBlk == 256, "the owner lookup below searches 256 slots in 8 steps");  // 
+  for (uint32_t e0 = 0; e0 < tot; e0 += H * kBlk) {
+    uint32_t owner[H], place[H];
+    bool live[H];
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+      const uint32_t ee = e0 + threadIdx.x + h * kBlk;
+      live[h] = ee < tot;
+      const uint32_t e = live[h] ? ee : 0u;
+      // the slot holding entry e: the last t with s_off[t] <= e (empty slots share offsets)
+      uint32_t lo = 0, hi = kBlk;  // s_off[lo] <= e < s_off[hi]
+#pragma unroll
+      for (int it = 0; it < 8; ++it) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (s_off[mid] <= e) lo = mid;
+        else hi = mid;
+      }
+      owner[h] = lo;
+      place[h] = e - s_off[lo];
+    }
+    f(owner, place, live);
+  }
+}
+
 // Verification against the text (lf_exact indexes that keep the full suffix array and the
 // text in HBM: DevIndex::vsa / vtext).  Row r of [sp, ep) survives the k remaining steps
 // iff its chain spells P[k-1], ..., P[0]; LF^t(r) is the row of the rotation SA[r] - t, so
@@ -1180,6 +1258,11 @@ constexpr uint64_t kWalkRowMask = (1ull << kWalkAdjShift) - 1;
 constexpr uint32_t kLocVerRelBits = 12;
 constexpr uint64_t kLocVerMaxK = (1u << 10) - 1;
 
+// Position p moved back by adj characters, mod n (adj <= n): where a window's match starts,
+// adj characters before the position of its row
+__device__ __forceinline__ uint64_t pos_back(uint64_t p, uint64_t adj, uint64_t n) {
+  return p >= adj ? p - adj : p + n - adj;
+}
 // rows, adjustment and match bits of a window record (s & kLocCtx)
 __device__ __forceinline__ void loc_window(uint64_t s, uint64_t& r0, uint64_t& adj, uint32_t& rel) {
   r0 = s & kLocRowMask;

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(kBlk) void k_locate_sa(const uint32_t* __restrict__
       const uint64_t adj = rows.adj;
       for (uint64_t j = 0; j < c; ++j) {
         const uint64_t p = load_sa(sa, rows.next());
-        st_out(out + a + j, p >= adj ? p - adj : p + n - adj);
+        st_out(out + a + j, pos_back(p, adj, n));
       }
     } else if (c <= kLocSmall) {  // consecutive rows: the lane's reads share their sectors
       for (uint64_t j = 0; j < c; ++j) st_out(out + a + j, (uint64_t)sa[rows.next()]);
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(kBlk) void k_walk(DevIndex ix, const uint64_t* __re
       phase = kWalk;
     } else if (phase == kSample) {
       const uint64_t s = walk_start(smp, steps, n);  // :147-153
-      st_out(out + j, steps_only ? steps : s >= adj ? s - adj : s + n - adj);
+      st_out(out + j, steps_only ? steps : pos_back(s, adj, n));
       phase = kFetch;
     } else if (phase == kWalk) {
       // loop condition of fm_index.cpp:130: stop at a sampled row or after n steps
@@ -263,7 +263,7 @@ __global__ __launch_bounds__(kBlk) void k_walk_lines(DevIndex ix, const uint64_t
       }
     } else if (phase == kSample) {
       const uint64_t s = walk_start(smp, steps, n);  // :147-153
-      st_out(out + j, steps_only ? steps : s >= adj ? s - adj : s + n - adj);
+      st_out(out + j, steps_only ? steps : pos_back(s, adj, n));
       if (jn < end) {
         j = jn;
         pos = row & kWalkRowMask;

@@ -10,6 +10,10 @@
 namespace fmx {
 namespace {
 
+// the walk lines of a kernel's kPos / kWalk parameter: 1 narrow (WalkLine), 2 wide (WalkLineW)
+template <int kPos>
+using WalkLineOf = std::conditional_t<kPos == 1, WalkLine, WalkLineW>;
+
 // the rows the reference samples (row % stride == 0) and their index in the SSA, for the
 // walk over the engine's own LF (k_walk); POW2: the stride is a power of two
 template <bool POW2>
@@ -208,7 +212,7 @@ __device__ __forceinline__ void walk_short_one(const DevIndex& ix, const NodeTab
     atomicMin(err, (unsigned long long)j);
     return;
   }
-  st_out(out + j, steps_only ? steps : s >= adj ? s - adj : s + n - adj);
+  st_out(out + j, steps_only ? steps : pos_back(s, adj, n));
 }
 
 // ---- the lockstep walk ----

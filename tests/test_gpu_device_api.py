@@ -462,8 +462,10 @@ def test_hbm_budget(kind, build_opts):
 
 
 def test_locate_one_call_many_tiles():
-    """The one-call locate's tile scan over more tiles than one round of k_scan_tiles
-    (> 32 k tiles of 512 patterns: 17 M patterns) equals the two-phase locate."""
+    """The one-call locate's tile scan over many blocks of the chained scan (17 M patterns:
+    33,204 tiles of 512 patterns, 33 blocks of k_scan_chained at 1,024 tiles each) equals the
+    two-phase locate.  (The one-block k_scan_tiles runs only past 2^20 tiles, more than
+    536,870,912 patterns: no test reaches it.)"""
     pkg = load_pkg()
     st = torch.cuda.current_stream().cuda_stream
     t = O.gen_dna(33, 200_000).tobytes()
