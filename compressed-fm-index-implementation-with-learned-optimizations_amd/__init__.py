@@ -40,6 +40,8 @@ QT_WALK_ROWS, QT_WALK_PERSISTENT, QT_GENERAL_INLANE, QT_GENERAL_LIST_ALL = 1 << 
 QT_MAP_LDS = 1 << 24
 # the largest mismatch bound of count_mismatches (include/cs_fmindex_approx.h CS_MM_MAX)
 CS_MM_MAX = 3
+# the largest bound of the seeded locate (include/cs_fmindex_approx_seeded.h CS_SEED_MAX_K)
+SEED_MAX_K = 15
 # best_dist of a pattern with no occurrence within k (include/cs_fmindex_approx_best.h CS_MM_NONE)
 CS_MM_NONE = 0xFF
 
@@ -220,6 +222,17 @@ SIGNATURES = {
                                                    _u64p, C.c_uint64, _u64p, _vp]),
     "cs_fm_locate_best_mismatch": (C.c_int, [_vp, C.c_char_p, C.c_uint64, C.c_uint32, _u8p, _u64p,
                                              C.c_uint64, _u64p]),
+    # include/cs_fmindex_approx_seeded.h (the same pairs for k <= SEED_MAX_K: seeds verified on the text)
+    "cs_fm_locate_mismatch_seeded_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_uint32, _vp,
+                                                      _vp, _vp, C.c_uint64, _u64p, _u64p, C.c_uint32, _vp]),
+    "cs_fm_locate_mismatch_seeded_batch": (C.c_int, [_vp, _u8p, _u64p, C.c_uint64, C.c_uint32, _u64p, _u64p,
+                                                     _u8p, C.c_uint64, _u64p, _u64p, _vp]),
+    "cs_fm_locate_mismatch_seeded": (C.c_int, [_vp, C.c_char_p, C.c_uint64, C.c_uint32, _u64p, _u8p,
+                                               C.c_uint64, _u64p]),
+    # its measurement twin (include/cs_fmindex_diag.h): the phase times
+    "cs_fm_locate_mismatch_seeded_phases_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                             _vp, _vp, _vp, C.c_uint64, _u64p, _u64p,
+                                                             C.c_uint32, C.POINTER(C.c_float), _vp]),
 }
 
 _lib = None
@@ -664,6 +677,62 @@ class FMIndex:
             return total.value, False
         _check(st)
         return total.value, True
+
+    # -- seeded locate within k mismatches (include/cs_fmindex_approx_seeded.h) ----
+    def locate_mismatches_seeded(self, pattern, k: int):
+        """-> (pos uint64[], dist uint8[]): locate_mismatches' pairs by pigeonhole seeds verified
+        against the text (cs_fm_locate_mismatch_seeded): pieces ascending, each piece's row
+        order.  k <= SEED_MAX_K < len(pattern); needs the byte text in HBM and an lf_exact index."""
+        _, pos, dist = self.locate_mismatches_seeded_batch([_bytes(pattern)], k)
+        return pos, dist
+
+    def locate_mismatches_seeded_batch(self, patterns=None, k: int = 1, buf=None, offs=None):
+        """-> (out_offs[npat + 1], pos, dist): the pairs of pattern q at
+        [out_offs[q], out_offs[q + 1]) (cs_fm_locate_mismatch_seeded_batch; a first call sizes
+        the output)."""
+        if patterns is not None:
+            buf, offs = pack_patterns(patterns)
+        buf = np.ascontiguousarray(buf, np.uint8)
+        if len(buf) == 0:
+            buf = np.zeros(1, np.uint8)
+        offs = np.ascontiguousarray(offs, np.uint64)
+        npat = len(offs) - 1
+        out_offs = np.zeros(npat + 1, np.uint64)
+        total = C.c_uint64()
+        st = lib().cs_fm_locate_mismatch_seeded_batch(self._h, _u8(buf), _u64(offs), npat, k, _u64(out_offs),
+                                                      None, None, 0, C.byref(total), None, None)
+        if st == CS_OK:
+            return out_offs, np.zeros(0, np.uint64), np.zeros(0, np.uint8)
+        if st != CS_ERR_CAPACITY:
+            _check(st)
+        pos = np.zeros(total.value, np.uint64)
+        dist = np.zeros(total.value, np.uint8)
+        _check(lib().cs_fm_locate_mismatch_seeded_batch(self._h, _u8(buf), _u64(offs), npat, k, _u64(out_offs),
+                                                        _u64(pos), _u8(dist), total.value, C.byref(total),
+                                                        None, None))
+        return out_offs, pos, dist
+
+    def locate_mismatch_seeded_device(self, d_pats, d_offs, npat, k, d_out_offs, d_out_pos, d_out_dist, cap,
+                                      fixed_m=0, flags=0, stream=0, phase_ms=None):
+        """Positions and distances of a device batch (cs_fm_locate_mismatch_seeded_device):
+        offsets into d_out_offs[npat + 1] and, when the total fits `cap`, d_out_pos / d_out_dist
+        -> (total, candidates, written).  d_offs or None for npat patterns of length fixed_m back
+        to back; cap = 0 with null outputs sizes; flags Q_* leave structures out (same results).
+        phase_ms: a list that receives the five phase times of the measurement twin
+        (cs_fm_locate_mismatch_seeded_phases_device)."""
+        total, cand = C.c_uint64(), C.c_uint64()
+        args = (self._h, d_pats or None, d_offs or None, fixed_m, npat, k, d_out_offs, d_out_pos or None,
+                d_out_dist or None, cap, C.byref(total), C.byref(cand), flags)
+        if phase_ms is None:
+            st = lib().cs_fm_locate_mismatch_seeded_device(*args, stream or None)
+        else:
+            ms = (C.c_float * 5)()
+            st = lib().cs_fm_locate_mismatch_seeded_phases_device(*args, ms, stream or None)
+            phase_ms[:] = list(ms)
+        if st == CS_ERR_CAPACITY:
+            return total.value, cand.value, False
+        _check(st)
+        return total.value, cand.value, True
 
     def locate_batch(self, patterns=None, limit: int = 100000, buf=None, offs=None):
         """-> (out_offs[npat+1], positions) with positions of pattern q in row order at

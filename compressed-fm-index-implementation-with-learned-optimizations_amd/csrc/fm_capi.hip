@@ -1344,6 +1344,189 @@ cs_status cs_fm_locate_mismatch(const cs_fm_index* h, const uint8_t* pattern, ui
   return s;
 }
 
+// ---- seeded locate within k mismatches (include/cs_fmindex_approx_seeded.h) ----
+// What its entry points check first, in this order: the handle (entering its device), the bound
+// k, the entry point's own pointer arguments, then what the handle must hold.
+static cs_status seeded_enter(const cs_fm_index* h, DeviceScope& dscope, uint32_t k, bool null_arg) {
+  cs_status s = check_handle(h, dscope);
+  if (s != CS_OK) return s;
+  if (k > CS_SEED_MAX_K) {
+    set_error("mismatch bound k must be at most CS_SEED_MAX_K = " + std::to_string(CS_SEED_MAX_K));
+    return CS_ERR_INVALID;
+  }
+  if (null_arg) return null_batch_pointer();
+  if (!h->lf_exact) {
+    set_error("seeded locate: the text has no unique smallest last symbol (the index is not lf_exact)");
+    return CS_ERR_UNSUPPORTED;
+  }
+  if (!h->d_dtext) {
+    set_error("seeded locate: the index does not keep the byte text in HBM (cs_fm_info.text_in_hbm)");
+    return CS_ERR_UNSUPPORTED;
+  }
+  return CS_OK;
+}
+
+static cs_status seeded_short_pattern(uint64_t q, uint32_t k) {
+  set_error("seeded locate: pattern " + std::to_string(q) + " is not longer than k = " + std::to_string(k));
+  return CS_ERR_INVALID;
+}
+
+// the structure flags the two phases of the exact locate honour (as cs_fm_locate_device's)
+static uint32_t seeded_flags(uint32_t flags) { return flags & ~(CS_Q_LONG | CS_Q_NO_LOC_RECORDS); }
+
+// the device batch; phase_ms: null, or the five phase times of cs_fm_locate_mismatch_seeded_phases_device
+static cs_status locate_seeded_device(const cs_fm_index* h, const uint8_t* d_pats, const uint64_t* d_offs,
+                                      uint64_t fixed_m, uint64_t npat, uint32_t k, uint64_t* d_out_offs,
+                                      uint64_t* d_out_pos, uint8_t* d_out_dist, uint64_t cap,
+                                      uint64_t* total, uint64_t* candidates, uint32_t flags, hipStream_t st,
+                                      float* phase_ms) {
+  DeviceScope dscope;
+  cs_status s = seeded_enter(h, dscope, k,
+                             !total || !d_out_offs || (cap && (!d_out_pos || !d_out_dist)) ||
+                                 (npat && !d_pats && !d_offs && fixed_m));
+  if (s != CS_OK) return s;
+  if (npat && !d_offs && fixed_m && fixed_m <= k) return seeded_short_pattern(0, k);
+  if ((s = null_pats_ok(d_pats, d_offs, npat, st)) != CS_OK) return s;
+  if (phase_ms)
+    for (int i = 0; i < 5; ++i) phase_ms[i] = 0.f;
+  if (!npat) {
+    *total = 0;
+    if (candidates) *candidates = 0;
+    FMX_HIP(hipMemsetAsync(d_out_offs, 0, 8, st));
+    FMX_HIP(hipStreamSynchronize(st));
+    return CS_OK;
+  }
+  struct Events {
+    hipEvent_t e[6] = {};
+    ~Events() {
+      for (hipEvent_t x : e)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } ev;
+  if (phase_ms)
+    for (hipEvent_t& x : ev.e) FMX_HIP(hipEventCreate(&x));
+  hipEvent_t* e = phase_ms ? ev.e : nullptr;
+  SeedPlan plan;
+  const uint32_t f = seeded_flags(flags);
+  if ((s = launch_seed_search(h, d_pats, d_offs, npat, k, d_offs ? 0 : fixed_m, f, st, plan, e)) != CS_OK)
+    return s;
+  if (candidates) *candidates = plan.ncand;
+  if ((s = launch_seed_verify(h, d_pats, npat, k, d_out_offs, f, st, plan, e)) != CS_OK) return s;
+  *total = plan.total;
+  if (phase_ms)
+    for (int i = 0; i < 4; ++i) FMX_HIP(hipEventElapsedTime(&phase_ms[i], e[i], e[i + 1]));
+  if (plan.total > cap) {
+    set_error("locate: capacity too small");
+    return CS_ERR_CAPACITY;
+  }
+  if (!plan.total) return CS_OK;
+  if ((s = launch_seed_emit(plan, d_out_pos, d_out_dist, st, e)) != CS_OK) return s;
+  if (phase_ms) {
+    FMX_HIP(hipEventSynchronize(e[5]));
+    FMX_HIP(hipEventElapsedTime(&phase_ms[4], e[4], e[5]));
+  }
+  return CS_OK;
+}
+
+cs_status cs_fm_locate_mismatch_seeded_device(const cs_fm_index* h, const uint8_t* d_pats,
+                                              const uint64_t* d_offs, uint64_t fixed_m, uint64_t npat,
+                                              uint32_t k, uint64_t* d_out_offs, uint64_t* d_out_pos,
+                                              uint8_t* d_out_dist, uint64_t cap, uint64_t* total,
+                                              uint64_t* candidates, uint32_t flags, void* stream) {
+  return locate_seeded_device(h, d_pats, d_offs, fixed_m, npat, k, d_out_offs, d_out_pos, d_out_dist, cap,
+                              total, candidates, flags, (hipStream_t)stream, nullptr);
+}
+
+cs_status cs_fm_locate_mismatch_seeded_phases_device(const cs_fm_index* h, const uint8_t* d_pats,
+                                                     const uint64_t* d_offs, uint64_t fixed_m,
+                                                     uint64_t npat, uint32_t k, uint64_t* d_out_offs,
+                                                     uint64_t* d_out_pos, uint8_t* d_out_dist,
+                                                     uint64_t cap, uint64_t* total, uint64_t* candidates,
+                                                     uint32_t flags, float* phase_ms, void* stream) {
+  if (!phase_ms) {
+    set_error("null phase_ms");
+    return CS_ERR_INVALID;
+  }
+  return locate_seeded_device(h, d_pats, d_offs, fixed_m, npat, k, d_out_offs, d_out_pos, d_out_dist, cap,
+                              total, candidates, flags, (hipStream_t)stream, phase_ms);
+}
+
+cs_status cs_fm_locate_mismatch_seeded_batch(const cs_fm_index* h, const uint8_t* pats,
+                                             const uint64_t* offs, uint64_t npat, uint32_t k,
+                                             uint64_t* out_offs, uint64_t* out_pos, uint8_t* out_dist,
+                                             uint64_t cap, uint64_t* total, uint64_t* candidates,
+                                             void* stream) {
+  DeviceScope dscope;
+  hipStream_t st = (hipStream_t)stream;
+  cs_status s = seeded_enter(h, dscope, k, !total || !out_offs || (npat && !offs));
+  if (s != CS_OK) return s;
+  if (!npat) {
+    *total = 0;
+    if (candidates) *candidates = 0;
+    out_offs[0] = 0;
+    return CS_OK;
+  }
+  if (!pats && offs[npat] != offs[0]) return null_batch_pointer();
+  if ((s = check_offsets(offs, npat)) != CS_OK) return s;
+  for (uint64_t q = 0; q < npat; ++q)
+    if (offs[q + 1] != offs[q] && offs[q + 1] - offs[q] <= k) return seeded_short_pattern(q, k);
+  StagedBatch b;  // staged once
+  if ((s = b.load(h, pats, offs, npat, st)) != CS_OK) return s;
+  StreamBuf d_oo, d_pos, d_dist;
+  FMX_HIP(d_oo.alloc((npat + 1) * 8, st));
+  SeedPlan plan;
+  if ((s = launch_seed_search(h, b.pats.as<uint8_t>(), b.offs.as<uint64_t>(), npat, k, 0, 0, st, plan)) != CS_OK)
+    return s;
+  if (candidates) *candidates = plan.ncand;
+  if ((s = launch_seed_verify(h, b.pats.as<uint8_t>(), npat, k, d_oo.as<uint64_t>(), 0, st, plan)) != CS_OK)
+    return s;
+  *total = plan.total;
+  {
+    HostPin po;
+    po.pin(h, out_offs, (npat + 1) * 8, st);
+    FMX_HIP(po.copy(out_offs, d_oo.p, (npat + 1) * 8, false, st));
+    FMX_HIP(hipStreamSynchronize(st));
+  }
+  if (plan.total > cap) {
+    set_error("locate output capacity too small");
+    return CS_ERR_CAPACITY;
+  }
+  if (!plan.total) return CS_OK;
+  if (!out_pos || !out_dist) {
+    set_error("null output buffer");
+    return CS_ERR_INVALID;
+  }
+  FMX_HIP(d_pos.alloc(plan.total * 8, st));
+  FMX_HIP(d_dist.alloc(plan.total, st));
+  if ((s = launch_seed_emit(plan, d_pos.as<uint64_t>(), d_dist.as<uint8_t>(), st)) != CS_OK) return s;
+  HostPin pp, pd;
+  pp.pin(h, out_pos, plan.total * 8, st);
+  pd.pin(h, out_dist, plan.total, st);
+  FMX_HIP(pp.copy(out_pos, d_pos.p, plan.total * 8, false, st));
+  FMX_HIP(pd.copy(out_dist, d_dist.p, plan.total, false, st));
+  FMX_HIP(hipStreamSynchronize(st));
+  return CS_OK;
+}
+
+cs_status cs_fm_locate_mismatch_seeded(const cs_fm_index* h, const uint8_t* pattern, uint64_t m, uint32_t k,
+                                       uint64_t* out_pos, uint8_t* out_dist, uint64_t cap, uint64_t* nout) {
+  if (!h) {  // (before *nout is touched)
+    set_error("null index handle");
+    return CS_ERR_INVALID;
+  }
+  if (!nout) {
+    set_error("null nout");
+    return CS_ERR_INVALID;
+  }
+  const uint64_t offs[2] = {0, m};
+  uint64_t oo[2] = {0, 0};
+  uint64_t total = 0;
+  cs_status s = cs_fm_locate_mismatch_seeded_batch(h, pattern, offs, 1, k, oo, out_pos, out_dist, cap, &total,
+                                                   nullptr, nullptr);
+  if (s == CS_OK || s == CS_ERR_CAPACITY) *nout = total;
+  return s;
+}
+
 cs_status cs_fm_locate_best_mismatch_device(const cs_fm_index* h, const uint8_t* d_pats,
                                             const uint64_t* d_offs, uint64_t fixed_m, uint64_t npat,
                                             uint32_t k, uint8_t* d_best_dist, uint64_t* d_out_offs,

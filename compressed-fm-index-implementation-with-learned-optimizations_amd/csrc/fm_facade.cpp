@@ -11,6 +11,7 @@
 #include "../../include/cs_fmindex_approx_best.h"
 #include "../../include/cs_fmindex_approx_best_locate.h"
 #include "../../include/cs_fmindex_approx_locate.h"
+#include "../../include/cs_fmindex_approx_seeded.h"
 
 namespace cs {
 namespace {
@@ -182,6 +183,25 @@ std::vector<std::pair<uint64_t, uint8_t>> FMIndex::locate_mismatches(std::string
   std::vector<uint64_t> pos(total);
   std::vector<uint8_t> dist(total);
   s = cs_fm_locate_mismatch(h_.get(), p, pattern.size(), k, pos.data(), dist.data(), total, &total);
+  if (s != CS_OK) raise(s);
+  res.reserve(total);
+  for (uint64_t i = 0; i < total; ++i) res.emplace_back(pos[i], dist[i]);
+  return res;
+}
+
+std::vector<std::pair<uint64_t, uint8_t>> FMIndex::locate_mismatches_seeded(std::string_view pattern,
+                                                                            unsigned k) const {
+  if (k > CS_SEED_MAX_K) throw std::invalid_argument("locate_mismatches_seeded: k must be at most 15");
+  std::vector<std::pair<uint64_t, uint8_t>> res;
+  if (!h_ || pattern.empty()) return res;  // an empty index or pattern, as locate_mismatches()
+  const uint8_t* p = reinterpret_cast<const uint8_t*>(pattern.data());
+  uint64_t total = 0;
+  cs_status s = cs_fm_locate_mismatch_seeded(h_.get(), p, pattern.size(), k, nullptr, nullptr, 0, &total);
+  if (s != CS_OK && s != CS_ERR_CAPACITY) raise(s);
+  if (!total) return res;
+  std::vector<uint64_t> pos(total);
+  std::vector<uint8_t> dist(total);
+  s = cs_fm_locate_mismatch_seeded(h_.get(), p, pattern.size(), k, pos.data(), dist.data(), total, &total);
   if (s != CS_OK) raise(s);
   res.reserve(total);
   for (uint64_t i = 0; i < total; ++i) res.emplace_back(pos[i], dist[i]);

@@ -17,6 +17,7 @@
 #include "../../include/cs_fmindex_approx_locate.h"
 #include "../../include/cs_fmindex_approx_best.h"
 #include "../../include/cs_fmindex_approx_best_locate.h"
+#include "../../include/cs_fmindex_approx_seeded.h"
 #include "fm_device.hpp"
 
 struct cs_fm_index {
@@ -269,7 +270,7 @@ class BuildOptScope {
 bool parse_build_options(const char* text, BuildOptions& o, std::string& err);
 
 // Query launches (fm_query.hip; locate's phase 2 in fm_walk.hip, the one-call locate's finish
-// in fm_locate.hip, the mismatch family's in fm_mismatch.hip).
+// in fm_locate.hip, the mismatch family's in fm_mismatch.hip, the seeded locate's in fm_seeded.hip).
 // the call's flags with the handle's tuning defaults
 inline uint32_t call_flags(const cs_fm_index* h, uint32_t flags) { return flags | h->tune; }
 // the index as one query sees it under the caller's query flags (fm_query.hip)
@@ -474,5 +475,35 @@ cs_status launch_best_locate_mm_emit(const cs_fm_index* h, const uint8_t* d_pats
                                      uint64_t fixed_m, const uint64_t* d_out_offs,
                                      const BestLeafPlan& plan, uint64_t* d_out_pos, uint32_t flags,
                                      hipStream_t st);
+
+// Seeded locate within k <= CS_SEED_MAX_K mismatches (cs_fmindex_approx_seeded.h; fm_seeded.hip),
+// in three steps with the caller's checks between them.  Search: the piece offsets
+// (k_seed_pieces) and the exact locate's phase 1 over the npat (k + 1) pieces with limit n;
+// plan.ncand = C is read back (synchronises st) and with it the lengths check: CS_ERR_INVALID
+// for a pattern with 0 < m <= k, nothing of the caller's written.  Verify: the positions of the
+// pieces' hits (launch_locate_walk), k_seed_verify (one candidate per lane), the scan of the
+// accepted candidates, d_out_offs[npat + 1]; plan.total and the walk's overrun word are read
+// back (synchronises st; CS_ERR_LF_OVERRUN as the exact locate).  Emit: d_out_pos[plan.total]
+// and d_out_dist[plan.total], asynchronous.  Candidate-sized temporaries that cannot be
+// allocated: CS_ERR_OOM with C in the message.  ev: null, or six events recorded at the start
+// and after the piece search, the positions, the verification, the scan with its offsets, and
+// the emit (the benchmark's split).
+struct SeedPlan {
+  StreamBuf poffs;      // [npieces + 1]: the pieces as patterns of d_pats
+  StreamBuf sp;         // [npieces]: their locate records
+  StreamBuf cand_offs;  // [npieces + 1]: the candidate CSR
+  StreamBuf cand_pos;   // [ncand]: the hit's position, then the alignment it proposes
+  StreamBuf res;        // [ncand + 1]: the distance, or 0xFF for a rejected candidate
+  StreamBuf slot;       // [ncand + 1]: the exclusive scan of the accepted candidates
+  uint64_t npieces = 0, ncand = 0, total = 0;
+};
+cs_status launch_seed_search(const cs_fm_index* h, const uint8_t* d_pats, const uint64_t* d_offs,
+                             uint64_t npat, uint32_t k, uint64_t fixed_m, uint32_t flags, hipStream_t st,
+                             SeedPlan& plan, hipEvent_t* ev = nullptr);
+cs_status launch_seed_verify(const cs_fm_index* h, const uint8_t* d_pats, uint64_t npat, uint32_t k,
+                             uint64_t* d_out_offs, uint32_t flags, hipStream_t st, SeedPlan& plan,
+                             hipEvent_t* ev = nullptr);
+cs_status launch_seed_emit(const SeedPlan& plan, uint64_t* d_out_pos, uint8_t* d_out_dist, hipStream_t st,
+                           hipEvent_t* ev = nullptr);
 
 }  // namespace fmx

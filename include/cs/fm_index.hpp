@@ -4,7 +4,7 @@
 // exceptions as cs::FMIndex (src/api/fm_index.hpp:11-67); the work runs on the GPU
 // through the C ABI in cs_fmindex.h (implementation: csrc/fm_facade.cpp inside
 // libcs_fmindex.so).  Additions: count_batch / locate_batch (one launch for many
-// patterns), count_mismatches / locate_mismatches / best_mismatch / locate_best_mismatch (occurrences within k substitutions, their positions, the smallest distance with a hit, and the positions at that distance), save_directory (the on-disk format open_directory reads), handle()
+// patterns), count_mismatches / locate_mismatches / best_mismatch / locate_best_mismatch (occurrences within k substitutions, their positions, the smallest distance with a hit, and the positions at that distance), locate_mismatches_seeded (the same positions for k <= 15 by seeds verified against the text), save_directory (the on-disk format open_directory reads), handle()
 // for the raw ABI, borrow() to wrap an ABI handle and serve() (resident
 // single-pattern server).  Errors are
 // std::runtime_error with the reference's message text ("locate: LF walk exceeded
@@ -71,6 +71,12 @@ class FMIndex {
   // within k, (0, {}) for an empty pattern over a non-empty text.  Throws as best_mismatch does.
   std::pair<int, std::vector<uint64_t>> locate_best_mismatch(std::string_view pattern,
                                                              unsigned k) const;
+  // Seeded locate (cs_fmindex_approx_seeded.h): locate_mismatches' pairs for k <= 15 by
+  // pigeonhole seeds verified against the text — pieces ascending, each piece's row order —
+  // on an index that keeps the byte text in HBM over a text with a unique smallest last
+  // symbol; the pattern must be longer than k.  Throws as locate_mismatches does
+  // (std::invalid_argument for k > 15, std::runtime_error for the rest).
+  std::vector<std::pair<uint64_t, uint8_t>> locate_mismatches_seeded(std::string_view pattern, unsigned k) const;
 
   // Serving mode for single-pattern count(): a resident wave answers from a pinned
   // mailbox instead of one kernel launch per call (cs_fm_serve_start / _stop).

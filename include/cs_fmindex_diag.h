@@ -46,6 +46,18 @@ cs_status cs_fm_locate_mismatch_phases_device(const cs_fm_index* h, const uint8_
                                               uint64_t cap, uint64_t* total, uint32_t flags,
                                               float* phase_ms, void* stream);
 
+/* Measurement twin of cs_fm_locate_mismatch_seeded_device (cs_fmindex_approx_seeded.h; same
+ * arguments and results): phase_ms[5] receives the device-event times, in ms, of the piece search, the positions, the
+ * verification, the scan with the offsets, and the emit (zeros for the phases a call does not
+ * reach). */
+cs_status cs_fm_locate_mismatch_seeded_phases_device(const cs_fm_index* h, const uint8_t* d_pats,
+                                                     const uint64_t* d_offs, uint64_t fixed_m,
+                                                     uint64_t npat, uint32_t k, uint64_t* d_out_offs,
+                                                     uint64_t* d_out_pos, uint8_t* d_out_dist,
+                                                     uint64_t cap, uint64_t* total,
+                                                     uint64_t* candidates, uint32_t flags,
+                                                     float* phase_ms, void* stream);
+
 /* Building blocks, for parity tests (host arrays in/out):
  *   level rank1   — BitVector::rank1 of wavelet level l (src/core/bitvector.cpp:165-230);
  *                   CS_ERR_UNSUPPORTED on an occurrence-line index (no levels)
